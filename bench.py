@@ -9,8 +9,19 @@ One step = one frame: host header update (fill_rand_buffer, mode.y) -> upload ->
 post-process pass (-> on N>1, gather of the image strips into rank 0 over RCCL, pipelined).
 N GPUs split the SAME frame into cost-balanced row strips (strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config b|c|d|e]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config b|c|d|e] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, settles the clock, warms up, times the K steps and prints the result line.
+--full adds everything else this file measures or checks, in runs of their own after the timed
+steps: the roofline figures (standalone launches, bursts, work counters, committed hardware-counter
+files), the other dispatch shape of modes 2-4, the reference's SSBO call shape (configs ref and
+a), the CPU baseline, and on N > 1 the bit-for-bit check of the first gathered frames.
+
+The clock is settled (--warm-ms) on a renderer of its own, so the frames the timed renderer has
+rendered before the timed steps, and with them its history ring, do not depend on how long the
+settling took: with the same arguments every run renders the same frames from the same state.
+--dump-outputs DIR writes what the last timed step left (dump_outputs below) for comparing builds.
 
 --gpus N means N ranks.  Without a launcher (WORLD_SIZE unset) and N > 1, bench.py starts
 torch.distributed.run with N processes on 127.0.0.1 itself, before anything touches the GPU, and
@@ -305,6 +316,35 @@ def load_traffic(cfg_name: str, src_sha1, root: Path | None = None):
     return found[0] if found else (None, None)
 
 
+DUMP_IMAGE_PIXELS = 1 << 21  # 32 MB of float4
+DUMP_BAND_ROWS = 64          # x W x 16 B per g-buffer array: 3.9 MB at 3840, 7.9 MB at 7680
+
+
+def dump_outputs(path: Path, rend, image: np.ndarray, slot: int) -> dict:
+    """--dump-outputs: what the last timed step computed, float32, < 64 MB in all.
+    image.npy            the frame a caller receives (Renderer.image(); on N > 1 the gathered frame):
+                         [H][W][4], or, of a frame over 32 MB, the [2^21][4] pixels at the sorted indices
+                         numpy.random.default_rng(0).choice(H * W, 2^21, replace=False) of the [H * W][4] frame
+    gbuffer_pixels.npy   the step's ring slot of the g-buffer (Renderer.download_rect), [W][rows][4]
+    gbuffer_normals.npy  each, over the 64 rows in the middle of this rank's strip
+    gbuffer_depth.npy"""
+    path.mkdir(parents=True, exist_ok=True)
+    px = np.asarray(image, np.float32).reshape(-1, 4)
+    sampled = len(px) > DUMP_IMAGE_PIXELS
+    if sampled:
+        px = px[np.sort(np.random.default_rng(0).choice(len(px), DUMP_IMAGE_PIXELS, replace=False))]
+    else:
+        px = px.reshape(image.shape)
+    np.save(path / "image.npy", np.ascontiguousarray(px))
+    y0 = rend.row_begin + max(0, (rend.R - DUMP_BAND_ROWS) // 2)
+    y1 = min(rend.row_end, y0 + DUMP_BAND_ROWS)
+    g = rend.download_rect(0, rend.W, y0, y1, image=False)
+    for name, a in (("pixels", g.pixels), ("normals", g.normals), ("depth", g.depth)):
+        np.save(path / f"gbuffer_{name}.npy", np.ascontiguousarray(a[slot]))
+    return {"dir": str(path), "image": "sample of 2^21 pixels" if sampled else "whole frame",
+            "gbuffer_rows": [y0, y1], "gbuffer_slot": slot}
+
+
 def rank_devices(world, rank, gpu, cdev):
     """every rank's (device index, PCI bus) on every rank: a world x 2 all-reduce"""
     import torch
@@ -378,11 +418,18 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="mode 1: run each frame's post-process after its AO pass on one stream, instead of "
                          "overlapping frame k's post-process with frame k+1's AO pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: roofline figures (standalone "
+                         "launches, bursts, work counters), the other dispatch shape of modes 2-4, the SSBO call shape "
+                         "(configs ref, a), the CPU baseline, and on N > 1 the check of the first gathered frames")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the last of them computed as DIR/<name>.npy "
+                         "(float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--warm-ms", type=float, default=300.0,
-                    help="after the warm-up frames, keep rendering (chunks of 8 frames) until this much wall "
-                         "time has passed on every rank, so the timed frames run at settled GPU clocks: the "
+                    help="before the warm-up frames, render on a renderer of its own (chunks of 8 frames) until this "
+                         "much wall time has passed on every rank, so the timed frames run at settled GPU clocks: the "
                          "clock ramps over ~10 ms of load (DVFS), longer than 20 strip frames at N = 8")
     ap.add_argument("--verify", action="store_true",
                     help="rank 0 also renders every frame whole and checks the gathered frames bit for bit "
@@ -588,10 +635,10 @@ def main():
     state = {"frame": 0, "ref_frame": 0, "mismatch": 0, "checked": 0, "verify_on": True, "phase": "warm-up"}
     ref = None
     # rank 0 checks gathered frames against a whole-frame render of its own: every frame with
-    # --verify, otherwise (N > 1) the first VERIFY_FIRST frames, during the warm-up, so every
-    # multi-GPU line carries correctness evidence without touching the timed region
+    # --verify, otherwise (--full, N > 1) the first VERIFY_FIRST frames, during the warm-up, so a
+    # full multi-GPU line carries correctness evidence without touching the timed region
     VERIFY_FIRST = 2
-    if (args.verify or world > 1) and rank == 0:
+    if (args.verify or (args.full and world > 1)) and rank == 0:
         ref = Renderer(W, H, S, spp, device=gpu)
         ref.set_stream(stream)
 
@@ -641,16 +688,24 @@ def main():
     # warm-up frames so the mode-1 temporal filter reads a full ring)
     ring_fill = max(0, rend.F - args.warmup)
     warm = args.warmup + ring_fill
-    tw = time.perf_counter()
-    if host_loop:
-        state["frame"] = rend.compute_frames(header, mode, state["frame"], warm, 7000, False)
-    else:
-        for k in range(warm):
-            step(k)
-    # settle the clock: chunks of 8 more frames until warm_ms has passed on every rank (the
-    # ranks agree on the chunk count, so the per-frame gathers stay matched)
+    # settle the clock first, on a renderer of its own (same strip, streams and settings, its own
+    # header and ring): chunks of 8 frames until warm_ms has passed on every rank (the ranks agree
+    # on the chunk count).  How many that takes differs from run to run; `rend` renders none of
+    # them, so its warm-up and timed frames, and the history they read, are the same in every run.
     settle = 0
-    while True:
+    srend = None
+    if args.warm_ms > 0:
+        srend = Renderer(W, H, S, spp, device=gpu, rows=(r0, r1))
+        if args.frame_batch > 0:
+            srend.set_frame_batch(args.frame_batch)
+        if args.no_tile_schedule:
+            srend.set_tile_schedule(False)
+        srend.set_stream(stream)
+        if pipeline:
+            srend.enable_pipelining(True, out_stream)
+        sheader, sframe = header.copy(), 0
+    tw = time.perf_counter()
+    while srend is not None:
         torch.cuda.synchronize()
         left = torch.tensor([args.warm_ms - (time.perf_counter() - tw) * 1e3], dtype=torch.float64, device=cdev)
         if world > 1:
@@ -658,12 +713,19 @@ def main():
         if float(left.item()) <= 0.0:
             break
         if host_loop:
-            state["frame"] = rend.compute_frames(header, mode, state["frame"], 8, 7000 + warm + settle, False)
+            sframe = srend.compute_frames(sheader, mode, sframe, 8, 7000 + settle, False)
         else:
-            for k in range(warm + settle, warm + settle + 8):
-                step(k)
+            for k in range(settle, settle + 8):
+                sheader.fill_rand_buffer(7000 + k) if mode in (1, 2) else sheader.moving_light(False)
+                sheader.set_mode(sframe, nobj)
+                srend.upload_header(sheader)
+                sframe = srend.dispatch(mode, sframe)
         settle += 8
-    warm += settle
+    if host_loop:
+        state["frame"] = rend.compute_frames(header, mode, state["frame"], warm, 7000, False)
+    else:
+        for k in range(warm):
+            step(k)
     if gather is not None:
         gather.finish()
         gather.gather_ms(reset=True)  # the timed frames' gathers only
@@ -720,6 +782,12 @@ def main():
     rend.enable_timing(False)
     progs = {1: [1, 2], 2: [3], 3: [4], 4: [5]}[mode]
     kstats = {p: rend.kernel_stats(p) for p in progs}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = warm + args.steps - 1
+        frame_img = rend.image() if gather is None else gather.frame(last).cpu().numpy()[:H]
+        dumped = dump_outputs(Path(args.dump_outputs), rend, frame_img, (state["frame"] - 1) % rend.F)
+    full = args.full
 
     # ---- the other dispatch shape of modes 2-4, the same frames through the same C++ loop, wall
     # clock: batched (up to F frames per launch, the image by each launch's last frame) beside
@@ -728,7 +796,7 @@ def main():
     fb_other = 32 if fb_timed == 1 else 1
     frames_per_launch = lambda fb: min(32, fb, rend.F)  # rt_compute_frames: min(kMaxBatch, batch, F)
     other = None
-    if host_loop and mode in (2, 3, 4) and not args.no_alt_dispatch:
+    if full and host_loop and mode in (2, 3, 4) and not args.no_alt_dispatch:
         rend.set_frame_batch(fb_other)
         # warm the other path first (its kernel instantiation's first launches)
         state["frame"] = rend.compute_frames(header, mode, state["frame"], 16, 7000 + warm, False)
@@ -746,38 +814,38 @@ def main():
                              "one launch and one image write per frame (the reference's shape, src/main.cpp:604)",
                  "measured": "C++ frame loop (rt_compute_frames), wall clock over the same number of frames"}
 
-    # ---- standalone kernel times (two frames, not overlapped) and work counters (two more,
-    # un-timed) on the timed frames' inputs -------------------------------------------------
-    if gather is not None:
-        gather.finish()
-    state["phase"] = "standalone"
-    if pipeline:
-        rend.enable_pipelining(False)
-        streams["out"] = stream
-    rend.enable_timing(True)
-    rend.reset_stats()
-    if host_loop:  # events recorded inside the C++ loop: no host submission gap in the bracket;
-        # F frames = one multi-frame launch for modes 3/4, as in the timed region
-        state["frame"] = rend.compute_frames(header, mode, state["frame"], rend.F, 7000 + warm, False)
-    else:
-        for k in range(warm, warm + 2):
-            step(k)
-    if gather is not None:
-        gather.finish()
-    solo = {p: rend.kernel_stats(p) for p in progs}
-    rend.enable_timing(False)
-    # kernel durations the way rocprof's sequential run sees them: a BURST of back-to-back
-    # launches of one program on the stream, two events around the burst (no per-launch event,
-    # no other program between; a per-launch event pair adds ~7 us, 20% of a config (b) frame),
-    # the last rendered slot re-rendered with its own header (a trace pass rewrites identical
-    # values; a post-process re-filters its previous output: the same flag-, history- and
-    # byte-pattern, since those follow the normals and depth)
-    # the bursts below re-run the last slot's programs in place (a post-process re-filters its own
-    # output), so the ring no longer holds the frames the whole-frame reference renders: the
-    # gathered frames are checked up to here (warm-up, timed and standalone frames), not after
-    state["verify_on"] = False
-    burst = {}
-    if True:
+    # ---- --full: standalone kernel times (two frames, not overlapped) and work counters (two
+    # more, un-timed) on the timed frames' inputs -------------------------------------------
+    solo, burst, counts, ncount = {}, {}, None, 2
+    if full:
+        if gather is not None:
+            gather.finish()
+        state["phase"] = "standalone"
+        if pipeline:
+            rend.enable_pipelining(False)
+            streams["out"] = stream
+        rend.enable_timing(True)
+        rend.reset_stats()
+        if host_loop:  # events recorded inside the C++ loop: no host submission gap in the bracket;
+            # F frames = one multi-frame launch for modes 3/4, as in the timed region
+            state["frame"] = rend.compute_frames(header, mode, state["frame"], rend.F, 7000 + warm, False)
+        else:
+            for k in range(warm, warm + 2):
+                step(k)
+        if gather is not None:
+            gather.finish()
+        solo = {p: rend.kernel_stats(p) for p in progs}
+        rend.enable_timing(False)
+        # kernel durations the way rocprof's sequential run sees them: a BURST of back-to-back
+        # launches of one program on the stream, two events around the burst (no per-launch event,
+        # no other program between; a per-launch event pair adds ~7 us, 20% of a config (b) frame),
+        # the last rendered slot re-rendered with its own header (a trace pass rewrites identical
+        # values; a post-process re-filters its previous output: the same flag-, history- and
+        # byte-pattern, since those follow the normals and depth)
+        # the bursts below re-run the last slot's programs in place (a post-process re-filters its own
+        # output), so the ring no longer holds the frames the whole-frame reference renders: the
+        # gathered frames are checked up to here (warm-up, timed and standalone frames), not after
+        state["verify_on"] = False
         slot = (state["frame"] - 1) % rend.F
         # ~12 ms of launches per burst (AO at (d): 6, post: 24 ... hybrid at (b): 200)
         reps_for = lambda p: int(min(400, max(6, 12.0 / max(solo[p][1] / max(solo[p][0], 1), 0.01))))
@@ -792,20 +860,19 @@ def main():
             e1.record(stream)
             e1.synchronize()
             burst[prog] = (e0.elapsed_time(e1) / reps, reps)
-    rend.enable_counters(True)
-    rend.read_counters(reset=True)
-    ncount = 2
-    for k in range(warm, warm + ncount):
-        step(k)
-    if gather is not None:
-        gather.finish()
-    counts = rend.read_counters(reset=True)
-    rend.enable_counters(False)
+        rend.enable_counters(True)
+        rend.read_counters(reset=True)
+        for k in range(warm, warm + ncount):
+            step(k)
+        if gather is not None:
+            gather.finish()
+        counts = rend.read_counters(reset=True)
+        rend.enable_counters(False)
 
     t_max = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     host_max = torch.tensor([host_s], dtype=torch.float64, device=cdev)
     strip_ms = torch.zeros(world, dtype=torch.float64, device=cdev)
-    strip_ms[plan.strip_of(rank)] = sum(tot / max(n_l, 1) for n_l, tot in solo.values())  # standalone kernel ms
+    strip_ms[plan.strip_of(rank)] = sum(tot / max(n_l, 1) for n_l, tot in solo.values())  # standalone kernel ms (--full)
     # per rank: median and mean ms from "strip rendered" to "its gather transfers complete"
     g_ms = torch.zeros(world, 2, dtype=torch.float64, device=cdev)
     if gms:
@@ -818,11 +885,8 @@ def main():
         dist.all_reduce(g_ms)
     elapsed = float(t_max.item())
 
-    if rank == 0:
-        rays_per_frame = W * H * (spp if mode in (1, 2) else 1)
-        value = rays_per_frame * args.steps / elapsed / 1e6
-        ms = elapsed / args.steps * 1e3
-        dom = progs[0]
+    def roofline_report(dom, binfo):
+        """--full, rank 0: the dominant program's roofline entry and the committed traffic file it used."""
         # Kernel duration for the roofline: the HIP-event span of a launch.  Without pipelining
         # that is the timed region's average.  Pipelined, consecutive AO launches overlap (frame
         # k+1's AO fills frame k's tail), so a timed span is not a duration: the standalone
@@ -839,7 +903,6 @@ def main():
         sustained = FLOP_PER_TEST * tests / (elapsed / args.steps) / 1e12
         band_px = (r1 - r0 + (2 if mode in (1, 2) and world > 1 else 0)) * W
         hbm_alg = BYTES_PER_PIXEL[dom] * band_px / (avg_ms * 1e-3) / 1e9
-        binfo = build_info()
         # the committed PMC / SQ files are whole-frame launches: attached only at N = 1
         traffic_data, traffic_src = load_traffic(args.config, binfo.get("src_sha1")) if world == 1 else (None, None)
         # a counter run's values are per dispatch: with multi-frame launches (modes 2-4 in the C++
@@ -926,6 +989,14 @@ def main():
             roof["hardware_counters_note"] = hw_note
         if valu:
             roof["valu_issue"] = valu
+        return roof, traffic_data
+
+    if rank == 0:
+        rays_per_frame = W * H * (spp if mode in (1, 2) else 1)
+        value = rays_per_frame * args.steps / elapsed / 1e6
+        ms = elapsed / args.steps * 1e3
+        binfo = build_info()
+        roof, traffic_data = roofline_report(progs[0], binfo) if full else (None, None)
         out = {
             "metric": "Mrays/s + ms/frame at 3840x2160, 16 AO samples, 64 spheres; 1/2/4/8 GPU",
             "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
@@ -946,7 +1017,6 @@ def main():
                        + ((", one launch per frame" if fb_timed == 1 else
                            ", up to %d frames per launch (each writes its colour slot; the image by the launch's "
                            "last frame)" % frames_per_launch(fb_timed)) if host_loop and mode in (2, 3, 4) else "")},
-            "roofline": roof,
             # host time per frame inside the frame calls = enqueue + waits for a free staging
             # buffer (back-pressure: the host runs up to 8 uploads ahead of the GPU)
             "host_enqueue_ms_per_step": round(max(0.0, host_s * 1e3 - host_wait_ms) / args.steps, 4),
@@ -955,7 +1025,12 @@ def main():
             "tile_schedule": ("off: workgroups in the plain order" if args.no_tile_schedule else
                               "longest first (rt_set_tile_schedule: mode-4 tiles by the bounce rounds of recent "
                               "frames; state %d)" % rend.tile_schedule_state()),
+            "full": full,
         }
+        if full:
+            out["roofline"] = roof
+        if dumped is not None:
+            out["outputs"] = dumped
         if host_loop and mode in (2, 3, 4):
             out["dispatch"] = (("one launch and one image write per frame (rt_set_frame_batch(1)): the reference's "
                                 "dispatch shape (src/main.cpp:604)") if fb_timed == 1 else
@@ -965,13 +1040,14 @@ def main():
             if other is not None:
                 out["batched_dispatch" if fb_other > 1 else "per_frame_dispatch"] = other
         if balance_info is not None:
-            sm = strip_ms.cpu().tolist()
-            balance_info.update({"strip_ms": [round(t, 4) for t in sm], "imbalance": round(imbalance(sm), 4)})
+            if full:
+                sm = strip_ms.cpu().tolist()
+                balance_info.update({"strip_ms": [round(t, 4) for t in sm], "imbalance": round(imbalance(sm), 4)})
             out["config"]["balance"] = balance_info
         if ref is not None:
             out["verify"] = {"frames_checked": state["checked"], "mismatched": state["mismatch"],
-                             "what": ("every frame up to the kernel-time bursts (warm-up, settle, timed and standalone "
-                                      "frames)" if args.verify else f"the first {VERIFY_FIRST} frames (warm-up)")
+                             "what": ("every frame up to the kernel-time bursts (warm-up, timed and, with --full, "
+                                      "standalone frames)" if args.verify else f"the first {VERIFY_FIRST} frames (warm-up)")
                              + ": the gathered frame vs a whole-frame render on rank 0, bit for bit",
                              "diag": state.get("diag", [])[:6]}
         if world > 1:
@@ -997,7 +1073,7 @@ def main():
                 "link_model": links,
                 "predicted_frame_ms": balance_info["predicted_frame_ms"] if balance_info else None}
             out["launched_by"] = os.environ.get("RTRT_BENCH_LAUNCHER", "external launcher")
-        if mode == 1:
+        if full and mode == 1:
             # standalone launches: in the pipelined timed region the post-process shares the GPU
             # with the next frame's AO pass, so its event span is not a kernel duration
             pms = burst[2][0]
@@ -1021,15 +1097,17 @@ def main():
                                     "traffic": traffic_data.get("2") if traffic_data else None,
                                     "traffic_over_model": (round(traffic_data["2"] / post_bytes, 3)
                                                            if traffic_data and traffic_data.get("2") else None)}
-        if world == 1 and args.config in ("ref", "a"):
+        if full and world == 1 and args.config in ("ref", "a"):
             out["ssbo_path"] = ssbo_path(args.config, gpu)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
             except Exception as e:  # the checker must not take the GPU number down with it
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
         print(json.dumps(out), flush=True)
     rend.close()
+    if srend is not None:  # (kept until here: freeing its ring idles the GPU, and the --full launches want settled clocks)
+        srend.close()
     if world > 1:
         dist.destroy_process_group()
 

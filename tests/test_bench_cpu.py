@@ -85,3 +85,56 @@ def test_launch_ranks_returns_none_when_not_launching(monkeypatch):
     assert bench.launch_ranks(["--gpus", "1"]) is None
     monkeypatch.setenv("WORLD_SIZE", "2")
     assert bench.launch_ranks(["--gpus", "2"]) is None
+
+
+class _FakeRenderer:
+    """The part of Renderer that dump_outputs uses: a strip of rows [row_begin, row_end)."""
+
+    def __init__(self, W, r0, r1, F=8):
+        self.W, self.F, self.row_begin, self.row_end, self.R = W, F, r0, r1, r1 - r0
+        self.asked = None
+
+    def download_rect(self, x0, x1, y0, y1, pixels=True, normals=True, depth=True, image=True):
+        import numpy as np
+        from real_time_ray_tracer_amd.host import GBuffer
+
+        assert self.row_begin <= y0 < y1 <= self.row_end and (x0, x1) == (0, self.W) and not image
+        self.asked = (y0, y1)
+        shp = (self.F, x1 - x0, y1 - y0, 4)
+        slot = np.arange(self.F, dtype=np.float32).reshape(self.F, 1, 1, 1)
+        return GBuffer(np.zeros(shp, np.float32) + slot, np.ones(shp, np.float32) + slot,
+                       np.full(shp, 2.0, np.float32) + slot, None)
+
+
+def test_dump_outputs_small_frame_is_written_whole(tmp_path):
+    import numpy as np
+
+    img = np.arange(48 * 64 * 4, dtype=np.float32).reshape(48, 64, 4)
+    r = _FakeRenderer(64, 0, 48)
+    info = bench.dump_outputs(tmp_path / "out", r, img, 5)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == [
+        "gbuffer_depth.npy", "gbuffer_normals.npy", "gbuffer_pixels.npy", "image.npy"]
+    got = np.load(tmp_path / "out" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    assert r.asked == (0, 48) and info["gbuffer_rows"] == [0, 48] and info["gbuffer_slot"] == 5
+    for name, base in (("pixels", 0.0), ("normals", 1.0), ("depth", 2.0)):  # the step's slot only
+        a = np.load(tmp_path / "out" / f"gbuffer_{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (64, 48, 4) and (a == base + 5).all()
+
+
+def test_dump_outputs_large_frame_is_a_fixed_sample_under_64_mb(tmp_path):
+    """A frame over 32 MB (here 2^21 + 4096 pixels) is written as the same 2^21 pixels every time,
+    the g-buffer over 64 rows in the middle of the strip; everything together stays under 64 MB."""
+    import numpy as np
+
+    W, r0, r1 = 4096, 100, 100 + 513
+    img = np.random.default_rng(1).random((r1 - r0, W, 4), dtype=np.float32)
+    r = _FakeRenderer(W, r0, r1)
+    bench.dump_outputs(tmp_path / "a", r, img, 0)
+    bench.dump_outputs(tmp_path / "b", r, img.copy(), 0)
+    a, b = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "b" / "image.npy")
+    assert a.shape == (1 << 21, 4) and a.dtype == np.float32 and np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(0).choice(img.shape[0] * W, 1 << 21, replace=False))
+    assert np.array_equal(a, img.reshape(-1, 4)[idx])
+    assert r.asked == (100 + (513 - 64) // 2, 100 + (513 - 64) // 2 + 64)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) < 64 << 20

@@ -18,7 +18,7 @@ ROOT = Path(__file__).resolve().parents[1]
 def test_bench_gpus_2_renders_on_2_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "c",
-                        "--steps", "4", "--warmup", "2", "--warm-ms", "50", "--no-cpu-baseline", "--no-alt-dispatch",
+                        "--full", "--steps", "4", "--warmup", "2", "--warm-ms", "50", "--no-cpu-baseline", "--no-alt-dispatch",
                         "--dist-timeout", "100"], capture_output=True, text=True, timeout=110, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The bench line's kernel_ms against rocprof's own durations of the same launches, from a
-rocprofv3 --kernel-trace CSV of `bench.py ... --no-cpu-baseline` and that run's JSON line.
+rocprofv3 --kernel-trace CSV of `bench.py --full ... --no-cpu-baseline` and that run's JSON line.
 
 bench.py times each program of the frame (mode 1: the AO pass, then the post-process) as a burst
 after the timed region: 1 warm-up launch + `burst_launches` back-to-back launches between two

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Summarise a rocprofv3 kernel trace of `bench.py --warmup W --steps K` for profiles/:
+"""Summarise a rocprofv3 kernel trace of `bench.py --full --warmup W --steps K` for profiles/:
 per-launch durations of the renderer's kernels in dispatch order and the mean over the timed
 launches (W warm-up first, then K timed, then 2 standalone frames (not overlapped), then the 2
 counted frames), to compare with the bench line's live HIP-event kernel_ms and
