@@ -1,6 +1,7 @@
 # Build the MI355X library (HIP, gfx950) and the CPU oracle (test infrastructure).
 #   make            -> real_time_ray_tracer_amd/librtrt.so, oracle/build/librt_oracle.so, build/rt_headless
 #   make lib|oracle|headless|clean
+#   make b1sort0    -> build/v_b1sort0/librtrt.so: the library with RT_B1_SORT=0 (test infrastructure)
 #   make ablib      -> build/librtrt_ab.so: the same shim over tools/ab/rt_kernels_ab.hip, the launcher
 #                      with the experimental A/B kernels and their RTRT_* environment switches
 #                      (tools/ab.py: RTRT_LIB=build/librtrt_ab.so); never part of librtrt.so
@@ -61,6 +62,11 @@ $(ABLIB): $(OBJDIR)/rt_kernels_ab.o $(OBJDIR)/rt_shim.o $(OBJDIR)/rt_host.o $(OB
 
 ablib: $(ABLIB)
 
+# The library built with RT_B1_SORT=0 (the AO pools' samples in item order, no sort instantiation
+# launched): tests/test_gpu_ao_sort.py compares it with the default build  -> build/v_b1sort0/librtrt.so
+b1sort0:
+	$(MAKE) variant V=b1sort0 VFLAGS=-DRT_B1_SORT=0
+
 # A compile-time variant of the production library for tools/ab.py --libs (same sources, extra
 # defines):  make variant V=post32x8 VFLAGS="-DRT_POST_BWX=4 -DRT_POST_BWY=1"  -> build/v_post32x8/librtrt.so
 variant:
@@ -84,4 +90,4 @@ $(OBJDIR):
 clean:
 	rm -rf build oracle/build $(LIB)
 
-.PHONY: all lib oracle headless ablib variant clean
+.PHONY: all lib oracle headless ablib variant b1sort0 clean

@@ -1062,9 +1062,9 @@ enum { PRIM_HIT = 0, PRIM_MISS = 1, PRIM_EMISSIVE = 2 };
 // LDS layout of ao_batch_kernel, in bytes.  Every offset is a compile-time constant when spp
 // is (SPPC), so the kernel then holds no LDS addresses in scalar registers.
 struct BatchLds {
-  int prec, sres, pstop, pkind, perm, cmask, rls, geol, total;
+  int prec, sres, pstop, pkind, perm, order, cmask, rls, geol, total;
 };
-__host__ __device__ constexpr BatchLds batch_lds(int spp, int pool, int ntail, bool rls_lds = true) {
+__host__ __device__ constexpr BatchLds batch_lds(int spp, int pool, int ntail, bool rls_lds = true, bool sort = false) {
   const int TP = pool / spp > 0 ? pool / spp : 1, NS = TP * spp;
   BatchLds L{};
   L.prec = 0;                                   // [TP] float4: first-segment (normal, t) of sample 0
@@ -1072,7 +1072,8 @@ __host__ __device__ constexpr BatchLds batch_lds(int spp, int pool, int ntail, b
   L.pstop = L.sres + 12 * NS;                   // [TP] int: max (aa << 16 | stop) of the stop writes
   L.pkind = L.pstop + 4 * TP;                   // [TP] int
   L.perm = L.pkind + 4 * ((TP + 1) & ~1);       // [64] int: live rank -> lane of the prepared batch
-  L.cmask = (L.perm + 256 + 7) & ~7;            // [32] u64: primary cull mask (nobj <= 2048)
+  L.order = L.perm + 256;                       // [pool] u8: batch slot -> item (RT_B1_SORT instantiations only)
+  L.cmask = (L.order + (sort ? pool : 0) + 7) & ~7;  // [32] u64: primary cull mask (nobj <= 2048)
   L.rls = (L.cmask + 8 * 32 + 15) & ~15;        // [2 spp] float4: rand_buffer
   L.geol = L.rls + (rls_lds ? 32 * spp : 0);   // [ntail] float4: sphere table (split tail rounds)
   L.total = L.geol + 16 * ntail;
@@ -1124,10 +1125,25 @@ __host__ __device__ constexpr BatchLds batch_lds(int spp, int pool, int ntail, b
 #ifndef RT_B1_CREAD
 #define RT_B1_CREAD 1
 #endif
+// A pool's samples dealt to its 64-lane batches by bounce direction instead of in item order
+// (SORT instantiations): the batches of a pool then each cover about a quarter of the hemisphere,
+// and the batched first bounce's cone keeps fewer spheres (tools/explore/b1_sort_sim.py).  Before
+// the first batch the wave computes hemi = get_pt_within_unit_sphere for all of the pool's samples
+// (it depends on (aa, pixel, rand_buffer) only), parks it in the sample's three sres slots (free
+// until finish(it); prepare() reads it back first), and counting-sorts the items by hemi's octant,
+// the 8 bins in Gray-code order (neighbouring bins differ in one sign), item order inside a bin:
+// order[slot] = item.  prepare() then takes bitem = order[next + lane].  Every sample's path is a
+// function of its item only and the cone, cull and pre-test are conservative filters visited in
+// ascending sphere order, so images and g-buffers are bit-identical; only the executed-tests and
+// row-cost counters change.  1 = on for the scenes launch_production selects (kB1SortMinObj);
+// 0 = no SORT instantiation is launched (the A/B build).
+#ifndef RT_B1_SORT
+#define RT_B1_SORT 1
+#endif
 constexpr int kAoMinWaves = RT_AO_MINW;
 template <int MINW, bool LAZY = true, int POOL = kPool, int ABL = 0, bool TAIL = false, bool B1 = false,
           int SPPC = 0, bool PT = false, bool CNT = true, bool PL = false, bool MF = false, bool CL = true, int DC = 0,
-          bool CLON = false, bool PTW = false>
+          bool CLON = false, bool PTW = false, bool SORT = false>
 __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const float4* __restrict__ geo) {
   if (RT_START_PRIO) __builtin_amdgcn_s_setprio(1);
   // CNT = false: the work counters compiled out (timed launches pass none): fewer live scalars
@@ -1153,13 +1169,15 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
   // PTW (scenes above kTailMaxObj spheres): the first bounce's pre-test rows one 64-sphere word at a
   // time in LDS, the split tail rounds on the global table, and rand_buffer read from global memory
   // (its LDS copy would not leave room for the rows at 7 waves per SIMD with spp 64)
-  const BatchLds LO = batch_lds(spp, POOL, 0, !PTW);
+  static_assert(!SORT || (LAZY && POOL % 64 == 0 && POOL <= 256), "SORT: hemi is read back from LDS; items are bytes");
+  const BatchLds LO = batch_lds(spp, POOL, 0, !PTW, SORT);
   char* lbase = (char*)lds;
   float4* prec = (float4*)(lbase + LO.prec);
   float* sres = (float*)(lbase + LO.sres);
   int* pstop = (int*)(lbase + LO.pstop);
   int* pkind = (int*)(lbase + LO.pkind);
   int* perm = (int*)(lbase + LO.perm);
+  unsigned char* order = (unsigned char*)(lbase + LO.order);  // SORT
   unsigned long long* cmask = (unsigned long long*)(lbase + LO.cmask);
   float4* rls = (float4*)(lbase + LO.rls);
   if (!PTW)
@@ -1405,6 +1423,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
     if (ABL == 3) { tsec[6] += (unsigned long long)ncull; tsec[7] += 1; }
     exec_tests += (unsigned long long)ncull;
     if (bitem < total) {
+      if (SORT) bitem = order[bitem];  // the pool's samples in bounce-direction order (RT_B1_SORT)
       const int lp = div_spp(bitem), aa = bitem - lp * spp;
       int x, y;
       pool_xy(lp, x, y);
@@ -1491,7 +1510,8 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
       ++nseg;
       // (every hit, emissive or not: only non-emissive hits use it, but waiting for the hit's flags
       // first cost a memory round trip, and a wave with any non-emissive hit computes it anyway)
-      if (LAZY && ind != -1) bhemi = hemisphere();
+      // (SORT: computed by the pool's pre-pass and parked in the sample's sres slots, which finish() overwrites)
+      if (LAZY && ind != -1) bhemi = SORT ? mk(sres[bitem], sres[NS + bitem], sres[2 * NS + bitem]) : hemisphere();
       live = shade(ind, t, bpos, bdir, bhemi, br, bg, bb, D, bitem, true);
     }
     bdepth = D - 1;
@@ -1648,6 +1668,91 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
     next = next + 64 < total ? next + 64 : total;
     __syncthreads();  // perm[] visible to the whole wave
   };
+
+  if (SORT) {
+    // ---- RT_B1_SORT pre-pass: hemi of every sample into its sres slots, order[] by hemi's octant ---
+    // Counting sort over the cells (octant, chunk of 64 items), one cell per lane.  A lane's rank
+    // among the chunk's lanes of its octant is a masked popcount of the chunk's three sign ballots;
+    // the cell counts are scanned octant by octant (Gray-code order) and chunk by chunk inside an
+    // octant, so the order is the same from run to run (items ascending inside an octant).
+    // perm[] holds the cell table: it is free until the first prepare().
+    constexpr int NC = POOL / 64, NF = 3;
+    static_assert(NC * (1 << NF) <= 64, "one cell per lane");
+    const int ln = lane_id_here();
+    perm[ln] = 0;
+    __syncthreads();
+    int key[NC];  // per chunk: rank in the cell | cell << 8
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      key[c] = 0;
+      if (c * 64 < total) {  // wave-uniform
+        const int it = c * 64 + ln;
+        f3 h = mk(0.0f, 0.0f, 0.0f);  // (the lanes past total: octant 0, masked out below)
+        if (it < total) {
+          const int lp = div_spp(it), aa = it - lp * spp;
+          int x, y;
+          pool_xy(lp, x, y);
+          const float px = (float)x, py = (float)y;
+          // get_pt_within_unit_sphere(aa): prepare()'s hemisphere(), the same operations in the same order
+          const float4 f = rbuf[2 * aa], s = rbuf[2 * aa + 1];
+          float abe[3];
+          grandom_n<3>({f.x + px * s.z, f.z - px * s.z, s.x * px + s.z}, {f.y + py * s.w, f.w - py * s.w, s.y * py + s.w},
+                       abe);
+          h = normalize(mk(abe[0] * 2.0f - 1.0f, abe[1] * 2.0f - 1.0f, abe[2] * 2.0f - 1.0f));
+          sres[it] = h.x;
+          sres[NS + it] = h.y;
+          sres[2 * NS + it] = h.z;
+        }
+        // the chunk's lanes in this lane's octant (valid items only: the lanes past total are the
+        // chunk's highest, so they precede no valid lane, but they would count in octant 0's cell)
+        const int nv = total - c * 64;
+        const unsigned long long mv = nv >= 64 ? ~0ull : (1ull << nv) - 1;
+        unsigned own_lo = (unsigned)mv, own_hi = (unsigned)(mv >> 32);
+        unsigned oct = 0;  // bit k = sign bit of component k (as the ballots: -0 and NaN by their sign bit)
+        const float hc[NF] = {h.x, h.y, h.z};
+#pragma unroll
+        for (int k = NF - 1; k >= 0; --k) {
+          const int bits = __float_as_int(hc[k]);
+          const unsigned long long m = __ballot(bits < 0);
+          const unsigned sgn = (unsigned)(bits >> 31);
+          own_lo &= ~((unsigned)m ^ sgn);
+          own_hi &= ~((unsigned)(m >> 32) ^ sgn);
+          oct = oct << 1 | (unsigned)bits >> 31;
+        }
+        const int cell = (int)oct * NC + c;
+        const int r = (int)__builtin_amdgcn_mbcnt_hi(own_hi, __builtin_amdgcn_mbcnt_lo(own_lo, 0u));
+        if (it < total) perm[cell] = __popc(own_lo) + __popc(own_hi);  // (the same value from every lane of the cell)
+        key[c] = r | cell << 8;
+      }
+    }
+    __syncthreads();
+    {  // lane = cell (bin ln / NC, chunk ln % NC) in sorted order: exclusive scan of the counts
+      const int bin = ln / NC, c = ln % NC;
+      const bool in = ln < NC * (1 << NF);
+      // bin b holds octant b ^ (b >> 1): Gray code, neighbouring bins' octants differ in one sign
+      const int cell = in ? (bin ^ (bin >> 1)) * NC + c : 0;
+      const int n = in ? perm[cell] : 0;
+      // inclusive scan on the DPP path: row_shr 1, 2, 4, 8 (zero fill) inside the rows of 16, then
+      // row_bcast:15 into rows 1, 3 and row_bcast:31 into rows 2, 3
+      int acc = n;
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x111, 0xf, 0xf, false);
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x112, 0xf, 0xf, false);
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x114, 0xf, 0xf, false);
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x118, 0xf, 0xf, false);
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x142, 0xa, 0xf, false);
+      acc += __builtin_amdgcn_update_dpp(0, acc, 0x143, 0xc, 0xf, false);
+      __syncthreads();  // every count is read
+      if (in) perm[cell] = acc - n;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int it = c * 64 + ln;
+      // slot < total: the cells partition the valid items, and a cell's base + its count <= total
+      if (it < total) order[perm[key[c] >> 8] + (key[c] & 255)] = (unsigned char)it;
+    }
+    __syncthreads();  // order[] and the parked hemi visible to the wave
+  }
 
   for (;;) {
     // ---- hand prepared live states to idle lanes; prepare more when the batch is used up --
@@ -2284,8 +2389,13 @@ size_t tab_lds_bytes(const FrameParams& p) { return (size_t)5 * (p.nobj > 0 ? p.
 // the sphere table fits in LDS (tl), with or without the work counters (cnt), with or without
 // planes (PL).
 constexpr int kRefDepth = 20;  // RECURSION_DEPTH, ao_compute.glsl:9
+// RT_B1_SORT: least spheres of a scene whose pools are sorted (RT_B1_SORT_MIN overrides: A/B builds)
+#ifndef RT_B1_SORT_MIN
+#define RT_B1_SORT_MIN 48
+#endif
+constexpr int kB1SortMinObj = RT_B1_SORT_MIN;
 
-template <int SPPC, bool PL, int DC = 0, bool CLON = false>
+template <int SPPC, bool PL, int DC = 0, bool CLON = false, bool SORT = false>
 inline void launch_batch(bool tl, bool cnt, dim3 g, dim3 b, size_t lds, hipStream_t stream, const FrameParams& q) {
   constexpr bool GT = RT_GLOBAL_TAIL;  // split tail rounds above kTailMaxObj spheres (global table)
   constexpr bool TLC = RT_TL_CLUSTERS;  // the cluster cull in the LDS-table (<= kTailMaxObj) instantiations
@@ -2293,19 +2403,19 @@ inline void launch_batch(bool tl, bool cnt, dim3 g, dim3 b, size_t lds, hipStrea
   if (q.mf_n > 0) {  // multi-frame mode-2 launch (never with counters: rt_compute_frames checks)
     g.y = (unsigned)q.mf_n;
     if (tl)
-      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, true, TLC, DC, CLON>), g, b, lds, stream, q, q.sph);
+      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, true, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
     else
-      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, true, true, DC, CLON, PTWV>), g, b, lds, stream, q, q.sph);
+      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, true, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
     return;
   }
   if (tl && cnt)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, true, PL, false, TLC, DC, CLON>), g, b, lds, stream, q, q.sph);
+    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, true, PL, false, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
   else if (tl)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, false, TLC, DC, CLON>), g, b, lds, stream, q, q.sph);
+    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, false, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
   else if (cnt)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, true, PL, false, true, DC, CLON, PTWV>), g, b, lds, stream, q, q.sph);
+    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, true, PL, false, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
   else
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, false, true, DC, CLON, PTWV>), g, b, lds, stream, q, q.sph);
+    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, false, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
 }
 
 // g-buffer layout conversion (rt_download / rt_upload_gbuffer, the host-buffer path of
@@ -2380,7 +2490,13 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const int TP = kPool / p.spp > 0 ? kPool / p.spp : 1;
     const long long pools = (npix + TP - 1) / TP;
     const bool tl = p.nobj <= kTailMaxObj;
-    const size_t psh = (size_t)batch_lds(p.spp, kPool, tl ? p.nobj : (RT_PT_WIDE ? 64 : 0), tl || !RT_PT_WIDE).total;
+    // RT_B1_SORT: scenes without planes of at least kB1SortMinObj spheres (below, the first bounce's
+    // cone keeps too few spheres for the sort to pay: 1920x1080, 16 spp, sorted against unsorted
+    // +2.5% / +2% / +4% at 16 / 24 / 32 spheres, -2% at 48, profiles/r07_ab_b1_sort_threshold.txt;
+    // plane scenes were not measured and stay unsorted)
+    const bool sort = RT_B1_SORT && !pl && p.nobj >= kB1SortMinObj;
+    const size_t psh =
+        (size_t)batch_lds(p.spp, kPool, tl ? p.nobj : (RT_PT_WIDE ? 64 : 0), tl || !RT_PT_WIDE, sort).total;
     const dim3 g((unsigned)pools), b(64);
     // timed launches pass no counters: the counter code is compiled out (fewer live scalars)
     const bool cnt = p.counters || p.row_counters;
@@ -2390,7 +2506,15 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     // scene of 16..256 spheres) also has its own instantiations for spp 16 and 64: with the depth
     // a constant and the rounds' plain full-scan fallback compiled out, fewer scalar registers are
     // spilled to vector lanes (each reload is a v_readlane on the bounce rounds' path)
-    if (!pl) {
+    if (sort) {
+      const bool ref_d = p.D == kRefDepth && p.ncl > 0;
+      if (p.spp == 16 && ref_d) launch_batch<16, false, kRefDepth, true, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+      else if (p.spp == 64 && ref_d) launch_batch<64, false, kRefDepth, true, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+      else if (p.spp == 16) launch_batch<16, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+      else if (p.spp == 64) launch_batch<64, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+      else if (p.spp == 4) launch_batch<4, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+      else launch_batch<0, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
+    } else if (!pl) {
       const bool ref_d = p.D == kRefDepth && p.ncl > 0;
       if (p.spp == 16 && ref_d) launch_batch<16, false, kRefDepth, true>(tl, cnt, g, b, psh, stream, q);
       else if (p.spp == 64 && ref_d) launch_batch<64, false, kRefDepth, true>(tl, cnt, g, b, psh, stream, q);

@@ -230,6 +230,9 @@ static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t strea
     hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 8, true, true, 16, true>), g, b, psh, stream, q, q.sph);
   else if (variant == 97 && tl && p.spp == 16)  // first-bounce / bounce-round event counts
     hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 7, true, true, 16, true>), g, b, psh, stream, q, q.sph);
+  else if (variant == 197 && tl && p.spp == 16)  // 97 with the pool's samples sorted by hemi's octant (RT_B1_SORT)
+    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 7, true, true, 16, true, true, false, false, true, 0, false, false, true>), g, b,
+                       (size_t)batch_lds(16, kPool, p.nobj, true, true).total, stream, q, q.sph);
   else if (variant == 93 && tl && p.spp == 16)  // section clocks of the production kernel
     hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, true, true, 16, true>), g, b, psh, stream, q, q.sph);
   else if (variant == 93 && tl)
