@@ -128,13 +128,7 @@ __device__ __forceinline__ void count_work(const FrameParams& P, bool active, in
 
 // Colour stores (g-buffer slot + image) non-temporal: written once, read by a later launch at
 // the earliest.  Hybrid (b) 26.25 -> 25.78 us, post_kernel (d) 0.311 -> 0.293 ms, AO and Phong
-// unchanged (profiles/r05u_*).  RT_NT_GBUF: the AO pass's normal and depth stores as well.
-#ifndef RT_NT_STORE
-#define RT_NT_STORE 1
-#endif
-#ifndef RT_NT_GBUF
-#define RT_NT_GBUF 0
-#endif
+// unchanged (profiles/r05u_*).  The AO pass's normal and depth stores stay plain stores.
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_nt(float4* p, float4 c) {
   __builtin_nontemporal_store(f4v{c.x, c.y, c.z, c.w}, (f4v*)p);
@@ -142,14 +136,11 @@ __device__ __forceinline__ void st_nt(float4* p, float4 c) {
 __device__ __forceinline__ void store_color(const FrameParams& P, float4* out_pix, float4* image, int x, int y,
                                             float4 c) {
   float4* const po = out_pix + (size_t)(y - P.band_row0) * P.W + x;
-  if (RT_NT_STORE) st_nt(po, c);
-  else *po = c;
+  st_nt(po, c);
   if (image) {
     int r = y - P.img_row0;
     if (r >= 0 && r < P.img_rows) {
-      float4* const pi = image + (size_t)r * P.W + x;
-      if (RT_NT_STORE) st_nt(pi, c);
-      else *pi = c;
+      st_nt(image + (size_t)r * P.W + x, c);
     }
   }
 }
@@ -167,12 +158,6 @@ __device__ __forceinline__ void store_color(const FrameParams& P, int x, int y, 
 __device__ __forceinline__ size_t dep_plane(const FrameParams& P) { return (size_t)P.band_rows * P.W; }
 __device__ __forceinline__ void dep_store(float4* base, size_t n, size_t off, float4 d) {
   float2* p = (float2*)base;
-  if (RT_NT_GBUF) {
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    __builtin_nontemporal_store(f2v{d.x, d.y}, (f2v*)(p + off));
-    __builtin_nontemporal_store(f2v{d.z, d.w}, (f2v*)(p + n + off));
-    return;
-  }
   p[off] = make_float2(d.x, d.y);
   p[n + off] = make_float2(d.z, d.w);
 }
@@ -194,13 +179,6 @@ __device__ __forceinline__ void nrm_store(float4* base, size_t n, size_t off, fl
     return;
   }
   float* p = (float*)base;
-  if (RT_NT_GBUF) {
-    __builtin_nontemporal_store(v.x, p + 3 * off);
-    __builtin_nontemporal_store(v.y, p + 3 * off + 1);
-    __builtin_nontemporal_store(v.z, p + 3 * off + 2);
-    __builtin_nontemporal_store(v.w, p + 3 * n + off);
-    return;
-  }
   p[3 * off] = v.x;
   p[3 * off + 1] = v.y;
   p[3 * off + 2] = v.z;
@@ -242,10 +220,6 @@ __device__ __forceinline__ FrameDst frame_dst(const FrameParams& P, int j) {
 // 4: -2.7%, 8: -17%; its waves are longer and the mirror bounces of a few tiles set the tail)
 // (tools/explore/r02m.sh).
 constexpr int kPhongFramesPerBlock = 4, kHybridFramesPerBlock = 1;
-#ifndef RT_HY_TPB
-#define RT_HY_TPB 1
-#endif
-constexpr int kHybridTilesPerBlock = RT_HY_TPB;  // tiles per hybrid block, one after another (A/B)
 
 template <int FPB>
 __device__ __forceinline__ int block_frames(const FrameParams& P, int& j0) {
@@ -420,15 +394,6 @@ __device__ __forceinline__ bool bounce_cone_keep_pt(const ConeB& c, float4 g, fl
 //      1e-2 (|p - c_i| + r_i), so both roots are negative by more than 10x the computed-root error
 //      (bounce_cone_misses (1)): never above the 1e-4 threshold.
 // NaN anywhere fails both tests and keeps the cluster.
-#ifndef RT_TL_CLUSTERS
-#define RT_TL_CLUSTERS 1
-#endif
-#ifndef RT_CL_MASKS
-#define RT_CL_MASKS 1
-#endif
-#ifndef RT_GLOBAL_TAIL
-#define RT_GLOBAL_TAIL 1  // config (e), 256 spheres: 140.6 -> 128.3 ms per frame (r03i)
-#endif
 #ifndef RT_CLUSTER_TAIL_MAX_G
 #define RT_CLUSTER_TAIL_MAX_G 8
 #endif
@@ -527,16 +492,18 @@ __device__ __forceinline__ unsigned long long plane_cone_mask(const FrameParams&
 // order, reading them on the scalar path (wave-uniform index).  PL: then the planes the cone
 // does not exclude.  Same result as closest_hit.  Must be called by every lane of the wave.
 // SKIP (timing ablation): cull only, no tests.
+// Camera rays only: every ray starts at the header's camera (P.cx, P.cy, P.cz).  The survivors are
+// tested from the per-frame camera-relative rows (P.camrel: camera - centre and its self dot,
+// computed on the host with the same float operations), so each test skips the three subtractions
+// and the self dot; rays from any other origin must use closest_hit / closest_hit_pf.
 template <bool PL, bool SKIP = false>
 __device__ __forceinline__ int closest_hit_cone(const FrameParams& P, const float4* __restrict__ geo, int nobj,
-                                                const ConeF& cone, f3 cam, f3 dir, float thr, float& t_out,
+                                                const ConeF& cone, f3 dir, float thr, float& t_out,
                                                 const float4* pre0 = nullptr) {
   float t = -1.0f;
   int ind = -1;
   const int lane = threadIdx.x & 63;
-  // cam is the header's camera (P.cx, P.cy, P.cz): the survivors are tested from the per-frame
-  // camera-relative rows (P.camrel: cam - centre and its self dot, computed on the host with the
-  // same float operations), so each test skips the three subtractions and the self dot
+  const f3 cam = mk(P.cx, P.cy, P.cz);
   const float4* const cr = P.camrel;
   auto word = [&](int w, bool keep) {
     unsigned long long m = uniform_mask(__ballot(keep));
@@ -580,26 +547,9 @@ __device__ __forceinline__ ConeF wave_tile_cone(const FrameParams& P, int bx, in
 #endif
 constexpr int kShadowConeMinObj = RT_SHADOW_CONE_MIN;
 // the binary64 occluder test of shadow_ray (p_compute.glsl:155-163) for one object's float t:
-// t > 0.0001 and length(dvec3(t * l)) < len.  With |l| within 2^-18.8 of 1 (checked per ray, see
-// shadow_bounds) the binary64 length is t |l| (1 +- 2^-51), so t < len (1 - 2^-12) and
-// t > len (1 + 2^-12) (float products, each within 2^-24) decide the test exactly; only t within
-// 2^-12 of len (an occluder at the light's distance) runs the binary64 sequence.
-// (RT_SHADOW_FAST=0: the binary64 sequence for every t, A/B builds)
-#ifndef RT_SHADOW_FAST
-#define RT_SHADOW_FAST 0
-#endif
-struct ShadowBounds {
-  float lo, hi;  // t < lo: occludes; t > hi: does not (finite bounds only when |l|^2 is within 2^-19 of 1)
-};
-__device__ __forceinline__ ShadowBounds shadow_bounds(f3 l, float len) {
-  const float l2 = dot(l, l);  // within 3 ulps of |l|^2
-  const bool ok = RT_SHADOW_FAST && fabsf(l2 - 1.0f) < 0x1p-19f;
-  return ok ? ShadowBounds{len * (1.0f - 0x1p-12f), len * (1.0f + 0x1p-12f)} : ShadowBounds{0.0f, INFINITY};
-}
-__device__ __forceinline__ bool shadow_occludes(float tf, f3 l, double dlen, ShadowBounds sb) {
+// t > 0.0001 and length(dvec3(t * l)) < len, the binary64 sequence for every such t
+__device__ __forceinline__ bool shadow_occludes(float tf, f3 l, double dlen) {
   if (!(tf > 0.0001f)) return false;  // (double)tf > (double)0.0001f, exactly
-  if (tf < sb.lo) return true;
-  if (tf > sb.hi) return false;
   const double t = (double)tf;
   const double dx = t * (double)l.x, dy = t * (double)l.y, dz = t * (double)l.z;
   return sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) < dlen;
@@ -614,15 +564,14 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
   const float len = sqrtf(dot(lv, lv));
   const f3 np = pos + 0.01f * l;
   const double dlen = (double)len;
-  const ShadowBounds sb = shadow_bounds(l, len);
   if (__ballot(need) == 0) return true;
   bool lit = true;
   if (PL)
     for (int k = 0; k < P.nplanes; ++k)
-      if (need && lit && shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen, sb)) lit = false;
+      if (need && lit && shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) lit = false;
   if (n <= kShadowConeMinObj) {  // small scenes: the cone costs more than it saves
     for (int k = 0; k < n; ++k) {
-      if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, geo[k]), l, dlen, sb)) lit = false;
+      if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, geo[k]), l, dlen)) lit = false;
     }
     return lit;
   }
@@ -644,7 +593,7 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
     const float4* const gw = geo + w;
     while (m) {
       const unsigned j = (unsigned)pop_lowest(m);
-      if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, gw[j]), l, dlen, sb)) lit = false;
+      if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, gw[j]), l, dlen)) lit = false;
     }
   };
   auto keep_row = [&](float4 g) {
@@ -675,12 +624,11 @@ __device__ __forceinline__ bool shadow_lit_sph(const FrameParams& P, const float
   const float len = sqrtf(dot(lv, lv));
   const f3 np = pos + 0.01f * l;
   const double dlen = (double)len;
-  const ShadowBounds sb = shadow_bounds(l, len);
   if (PL)
     for (int k = 0; k < P.nplanes; ++k)
-      if (shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen, sb)) return false;
+      if (shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) return false;
   for (int i = 0; i < n; ++i)
-    if (shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen, sb)) return false;
+    if (shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen)) return false;
   return true;
 }
 
@@ -707,7 +655,7 @@ __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* l
   int ind;
   if (ALLSPH) {
     const ConeF cone = wave_tile_cone<BWX, BWY>(P, bx, by);
-    ind = closest_hit_cone<PL>(P, geo, n, cone, cam, dir, 0.0f, t, pre0);
+    ind = closest_hit_cone<PL>(P, geo, n, cone, dir, 0.0f, t, pre0);
   } else {
     ind = closest_hit<ALLSPH>(geo, geo2, n, cam, dir, 0.0f, t);
   }
@@ -842,11 +790,10 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
     const float len = sqrtf(dot(lv, lv));
     const f3 np = curr + 0.01f * l;
     const double dlen = (double)len;
-    const ShadowBounds sb = shadow_bounds(l, len);
     if (PL)
       for (int k = pl; k < P.nplanes && !occ; k += G)
-        occ = shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen, sb);
-    for (int i = pl; i < n && !occ; i += G) occ = shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen, sb);
+        occ = shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen);
+    for (int i = pl; i < n && !occ; i += G) occ = shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen);
   }
   unsigned oc = occ ? 1u : 0u;
   for (int m = 1; m < G; m <<= 1) oc |= (unsigned)__shfl_xor((int)oc, m);
@@ -932,7 +879,7 @@ __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* 
     int ind0 = -1;
     bool lit0 = true;
     const ConeF cone = wave_tile_cone<BWX, BWY>(P, bx, by);
-    if (ABL != 2) ind0 = closest_hit_cone<PL, ABL == 3>(P, geo, n, cone, pos, dir, 0.001f, t0, pre0);
+    if (ABL != 2) ind0 = closest_hit_cone<PL, ABL == 3>(P, geo, n, cone, dir, 0.001f, t0, pre0);
     if (ABL == 0 || ABL >= 4) lit0 = shadow_lit_cone<PL>(P, geo, n, light, pos + t0 * dir, active && ind0 != -1, pre0);  // every lane takes part
     bool live = active && !segment(0, t0, ind0, lit0);
     // segments 1 .. D-1: bounce rounds with the whole wave
@@ -993,30 +940,7 @@ __global__ __launch_bounds__(64 * BWX * BWY) void hybrid_kernel(const unsigned* 
     else stage_shapes(P, lds);
     __syncthreads();
   }
-  if constexpr (kHybridTilesPerBlock == 2) {
-    // A/B builds: two tiles per block, half the waves.  Block b takes the tiles at positions b and
-    // n - 1 - b of the schedule's order (row order without one): one of the longest with one of
-    // the shortest, so block durations stay even.  The grid is gx x ceil(gy / 2).
-    const unsigned gx = gridDim.x, gy = (unsigned)(P.trace_rows + 8 * BWY - 1) / (8 * BWY), n = gx * gy;
-    const unsigned b = blockIdx.x + blockIdx.y * gx;
-#pragma unroll 1
-    for (int t = 0; t < 2; ++t) {
-      const unsigned u = t == 0 ? b : n - 1 - b;
-      if (b > n - 1 - b || (t == 1 && u == b)) break;  // (block-uniform; blocks past n / 2 have no tiles)
-      unsigned bx = u % gx, by = u / gx;
-      if (tord) {
-        const unsigned v = tord[u];
-        bx = v & 0xffffu;
-        by = v >> 16;
-      }
-      hybrid_tile<ALLSPH, PL, LT, ABL, BWX, BWY>(P, lds, hperm + 64 * (threadIdx.x >> 6), bx, by, frame_dst(P, blockIdx.z), gsph, gshp);
-    }
-  } else if constexpr (kHybridTilesPerBlock > 1) {  // A/B builds: TPB vertically adjacent tiles per block
-#pragma unroll 1
-    for (int t = 0; t < kHybridTilesPerBlock; ++t)
-      hybrid_tile<ALLSPH, PL, LT, ABL, BWX, BWY>(P, lds, hperm + 64 * (threadIdx.x >> 6), blockIdx.x,
-                                                 blockIdx.y * kHybridTilesPerBlock + t, frame_dst(P, blockIdx.z), gsph, gshp);
-  } else if constexpr (kHybridFramesPerBlock == 1) {  // no frame loop (the loop form costs 3-4% at (b))
+  if constexpr (kHybridFramesPerBlock == 1) {  // no frame loop (the loop form costs 3-4% at (b))
     // the host's tile schedule (longest first, from the previous frames' bounce rounds): the
     // few tiles whose mirror paths bounce for many rounds start early instead of setting the
     // launch's tail (config (b): 32.0 -> 25.4 us per frame with the reverse of row order, which
@@ -1059,100 +983,104 @@ enum { PRIM_HIT = 0, PRIM_MISS = 1, PRIM_EMISSIVE = 2 };
 // handed to idle lanes by ds_bpermute whenever lanes run out of work.  Bounce rounds then
 // run with (nearly) all lanes live, and no per-sample setup runs at partial utilisation.
 // ---------------------------------------------------------------------------------------
-// LDS layout of ao_batch_kernel, in bytes.  Every offset is a compile-time constant when spp
-// is (SPPC), so the kernel then holds no LDS addresses in scalar registers.
+// waves per SIMD the production AO kernel is compiled for (its register budget: 7 -> 72 VGPRs)
+#ifndef RT_AO_MINW
+#define RT_AO_MINW 7
+#endif
+constexpr int kAoMinWaves = RT_AO_MINW;
+// 1 = the pools' samples sorted by bounce direction (AoConfig::SORT) for the scenes ao_select picks
+// (kB1SortMinObj); 0 = no SORT instantiation is compiled (the A/B build, make b1sort0)
+#ifndef RT_B1_SORT
+#define RT_B1_SORT 1
+#endif
+
+// Compile-time configuration of ao_batch_kernel<C>: the defaults.  A configuration derives from
+// this struct (or from a production one, AoProd below) and overrides members by name.
+struct AoConfig {
+  static constexpr int SPPC = 0;       // spp as a constant (0: P.spp): constant LDS offsets and it / spp, fewer scalars
+  static constexpr int DC = 0;         // the depth as a constant (0: P.D)
+  static constexpr bool PL = false;    // the scene has planes: tested after the spheres of every segment, culled against the pool cone
+  static constexpr bool CLON = false;  // launched only with clusters (P.ncl > 0): the rounds' plain full scan is not compiled
+  static constexpr bool CNT = true;    // the work counters (false: compiled out, timed launches pass none)
+  static constexpr bool MF = false;    // frame blockIdx.y of a multi-frame mode-2 launch: its own rand_buffer and slots (FrameParams::mf_rb)
+  static constexpr bool LAZY = true;   // the empty-frustum shortcut; hemi computed after the primary hit, for hits only
+  static constexpr bool TAIL = false;  // split tail rounds (the pool's last <= 32 paths, a lane group each)
+  static constexpr bool B1 = false;    // a prepared batch's live paths take their first bounce together (bounce_cone)
+  static constexpr bool PT = false;    // with B1: the per-ray pre-test of the cone's survivors, rows in LDS; with TAIL: its sphere table in LDS
+  static constexpr bool PTW = false;   // with PT, above kTailMaxObj spheres: pre-test rows one 64-sphere word at a time, tail rounds
+                                       // on the global table, rand_buffer read from global memory (no LDS copy)
+  // The pool's samples dealt to its 64-lane batches by bounce direction instead of in item order:
+  // the batches then each cover about a quarter of the hemisphere and the batched first bounce's
+  // cone keeps fewer spheres (tools/explore/b1_sort_sim.py).  Before the first batch the wave
+  // computes hemi = get_pt_within_unit_sphere for all of the pool's samples (it depends on (aa,
+  // pixel, rand_buffer) only), parks it in the sample's three sres slots (free until finish(it);
+  // prepare() reads it back first), and counting-sorts the items by hemi's octant, the 8 bins in
+  // Gray-code order, item order inside a bin: order[slot] = item.  Every sample's path is a
+  // function of its item only and the cone, cull and pre-test are conservative filters visited in
+  // ascending sphere order, so images and g-buffers are bit-identical; only the executed-tests and
+  // row-cost counters change.
+  static constexpr bool SORT = false;
+  static constexpr int ABL = 0;        // diagnostics (A/B tools library): timing ablations, section clocks, event counts
+};
+// What the production launcher varies, as bits of AoProd's FLAGS / AoChoice::flags
+enum : unsigned {
+  AO_PL = 1,     // AoConfig::PL
+  AO_CLON = 2,   // AoConfig::CLON
+  AO_SORT = 4,   // AoConfig::SORT
+  AO_WIDE = 8,   // above kTailMaxObj spheres: AoConfig::PTW (else the sphere table fits the LDS rows)
+  AO_CNT = 16,   // AoConfig::CNT
+  AO_MF = 32,    // AoConfig::MF
+};
+// A production configuration: split tail rounds, the batched first bounce and its pre-test always.
+template <int SPPC_, int DC_, unsigned FLAGS>
+struct AoProd : AoConfig {
+  static constexpr int SPPC = SPPC_, DC = DC_;
+  static constexpr bool PL = FLAGS & AO_PL, CLON = FLAGS & AO_CLON, SORT = FLAGS & AO_SORT, PTW = FLAGS & AO_WIDE,
+                        CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF;
+  static constexpr bool TAIL = true, B1 = true, PT = true;
+};
+
+// LDS layout of ao_batch_kernel<C>, in bytes.  Every offset is a compile-time constant when spp
+// is (C::SPPC), so the kernel then holds no LDS addresses in scalar registers.
 struct BatchLds {
   int prec, sres, pstop, pkind, perm, order, cmask, rls, geol, total;
 };
-__host__ __device__ constexpr BatchLds batch_lds(int spp, int pool, int ntail, bool rls_lds = true, bool sort = false) {
-  const int TP = pool / spp > 0 ? pool / spp : 1, NS = TP * spp;
+__host__ __device__ constexpr BatchLds batch_lds_of(int spp, int ntail, bool rls_lds, bool sort) {
+  const int TP = kPool / spp > 0 ? kPool / spp : 1, NS = TP * spp;
   BatchLds L{};
   L.prec = 0;                                   // [TP] float4: first-segment (normal, t) of sample 0
   L.sres = 16 * TP;                             // [3][NS] float: per-sample r, g, b (channel-major)
   L.pstop = L.sres + 12 * NS;                   // [TP] int: max (aa << 16 | stop) of the stop writes
   L.pkind = L.pstop + 4 * TP;                   // [TP] int
   L.perm = L.pkind + 4 * ((TP + 1) & ~1);       // [64] int: live rank -> lane of the prepared batch
-  L.order = L.perm + 256;                       // [pool] u8: batch slot -> item (RT_B1_SORT instantiations only)
-  L.cmask = (L.order + (sort ? pool : 0) + 7) & ~7;  // [32] u64: primary cull mask (nobj <= 2048)
-  L.rls = (L.cmask + 8 * 32 + 15) & ~15;        // [2 spp] float4: rand_buffer
-  L.geol = L.rls + (rls_lds ? 32 * spp : 0);   // [ntail] float4: sphere table (split tail rounds)
+  L.order = L.perm + 256;                       // [kPool] u8: batch slot -> item (SORT only)
+  L.cmask = (L.order + (sort ? kPool : 0) + 7) & ~7;  // [32] u64: primary cull mask (nobj <= 2048)
+  L.rls = (L.cmask + 8 * 32 + 15) & ~15;        // [2 spp] float4: rand_buffer (rls_lds)
+  L.geol = L.rls + (rls_lds ? 32 * spp : 0);    // [ntail] float4: sphere table (split tail rounds) / pre-test rows
   L.total = L.geol + 16 * ntail;
   return L;
 }
+// configuration C's layout: no rand_buffer copy with PTW, order[] with SORT
+template <class C>
+__host__ __device__ constexpr BatchLds batch_lds(int spp, int ntail) {
+  return batch_lds_of(spp, ntail, !C::PTW, C::SORT);
+}
 
-// geo: the sphere table (P.sph).  PL: the scene has planes, tested after the spheres of every
-// segment (plane_candidate) and, for the primary rays, culled against the pool cone.
-// MF: frame blockIdx.y of a multi-frame mode-2 launch (FrameParams::mf_rb): its own rand_buffer
-// and slot buffers, the image by the launch's last frame only.
-// CL: the bounce-ray cluster cull of the later bounce rounds (P.ncl > 0); without it the rounds
-// test every sphere.
-// PTW (with PT, above kTailMaxObj spheres): the first bounce's pre-test rows one 64-sphere word at a
-// time, the split tail rounds on the global table, rand_buffer read from global memory (RT_PT_WIDE).
-// waves per SIMD the production AO kernel is compiled for (its register budget: 7 -> 72 VGPRs)
-#ifndef RT_AO_MINW
-#define RT_AO_MINW 7
-#endif
-// Scenes above kTailMaxObj spheres (config (e)): the first bounce's per-ray pre-test with its rows
-// one 64-sphere word at a time in LDS, rand_buffer read from global memory to make room for them.
-// Before, every cone survivor (95 of 256 per batch at (e)) ran the exact test; the pre-test leaves
-// ~15 that some lane passes (tools/explore/b1_pairs_sim.py).  Config (e) 121.5 -> 97.3 ms per
-// launch, bit-identical (profiles/r06t_*).  0 = the exact tests on every survivor (A/B builds).
-#ifndef RT_PT_WIDE
-#define RT_PT_WIDE 1
-#endif
-// the batched first bounce's exact tests deferred and merged over survivors with disjoint
-// pre-test masks (see the survivor loop): (d) 2.439 -> 2.414 ms, (c) 0.738 -> 0.730 ms
-// (profiles/r05z3_*); 0 = one exact pass per survivor that some lane passes (A/B builds)
-#ifndef RT_B1_DEFER
-#define RT_B1_DEFER 1
-#endif
-// The batched first bounce at wave issue priority 1 (s_setprio), every other phase at 0: among
-// the ready waves of a SIMD, those in the first bounce's latency-bound survivor loop issue first.
-// Per launch (d) 2.382 -> 2.349 ms, (c) 0.707 -> 0.698, (e) 93.0 -> 91.4; pipelined (d) frames
-// 2.172 -> 2.141 ms over three alternating rounds; images identical.  The later bounce rounds at
-// priority 1 too: level or worse; all of prepare(): worse pipelined (profiles/r06pm_*).
-#ifndef RT_B1_PRIO
-#define RT_B1_PRIO 1
-#endif
-// The pool's start (its LDS set-up, the rand_buffer copy and the primary cone cull: two dependent
-// global-load round trips) at priority 1 as well, so a new wave's loads issue ahead of the
-// resident waves' arithmetic: per launch (d) 2.441 -> 2.407 ms, (c) 0.714 -> 0.703, pipelined (d)
-// frames 2.144-2.154 -> 2.139-2.148 ms on top of RT_B1_PRIO; the split tail rounds at priority 1
-// instead: per launch -1.8% but pipelined frames +0.3% (profiles/r06px_*).
-#ifndef RT_START_PRIO
-#define RT_START_PRIO 1
-#endif
-#ifndef RT_B1_CREAD
-#define RT_B1_CREAD 1
-#endif
-// A pool's samples dealt to its 64-lane batches by bounce direction instead of in item order
-// (SORT instantiations): the batches of a pool then each cover about a quarter of the hemisphere,
-// and the batched first bounce's cone keeps fewer spheres (tools/explore/b1_sort_sim.py).  Before
-// the first batch the wave computes hemi = get_pt_within_unit_sphere for all of the pool's samples
-// (it depends on (aa, pixel, rand_buffer) only), parks it in the sample's three sres slots (free
-// until finish(it); prepare() reads it back first), and counting-sorts the items by hemi's octant,
-// the 8 bins in Gray-code order (neighbouring bins differ in one sign), item order inside a bin:
-// order[slot] = item.  prepare() then takes bitem = order[next + lane].  Every sample's path is a
-// function of its item only and the cone, cull and pre-test are conservative filters visited in
-// ascending sphere order, so images and g-buffers are bit-identical; only the executed-tests and
-// row-cost counters change.  1 = on for the scenes launch_production selects (kB1SortMinObj);
-// 0 = no SORT instantiation is launched (the A/B build).
-#ifndef RT_B1_SORT
-#define RT_B1_SORT 1
-#endif
-constexpr int kAoMinWaves = RT_AO_MINW;
-template <int MINW, bool LAZY = true, int POOL = kPool, int ABL = 0, bool TAIL = false, bool B1 = false,
-          int SPPC = 0, bool PT = false, bool CNT = true, bool PL = false, bool MF = false, bool CL = true, int DC = 0,
-          bool CLON = false, bool PTW = false, bool SORT = false>
-__global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const float4* __restrict__ geo) {
-  if (RT_START_PRIO) __builtin_amdgcn_s_setprio(1);
+// geo: the sphere table (P.sph).  The bounce-ray cluster cull of the later bounce rounds runs
+// whenever the launch has clusters (P.ncl > 0); without them the rounds test every sphere.
+template <class C>
+__global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P, const float4* __restrict__ geo) {
+  constexpr int SPPC = C::SPPC, DC = C::DC, ABL = C::ABL;
+  constexpr bool PL = C::PL, CLON = C::CLON, CNT = C::CNT, MF = C::MF, LAZY = C::LAZY, TAIL = C::TAIL, B1 = C::B1,
+                 PT = C::PT, PTW = C::PTW, SORT = C::SORT;
+  __builtin_amdgcn_s_setprio(1);  // the pool's start at issue priority 1, back to 0 after the primary cull
   // CNT = false: the work counters compiled out (timed launches pass none): fewer live scalars
   unsigned long long* const cnts = CNT ? P.counters : nullptr;
   unsigned long long* const rowc = CNT ? P.row_counters : nullptr;
   extern __shared__ float4 lds[];
   const int spp = SPPC ? SPPC : P.spp, W = P.W, D = DC ? DC : P.D, nobj = P.nobj;
   // CLON: launched only with clusters (P.ncl > 0), so the rounds' plain full-scan path is not compiled
-  const bool use_cl = CL && (CLON || P.ncl > 0);
+  const bool use_cl = CLON || P.ncl > 0;
   // this frame's buffers (the launch's frame unless MF)
   const int fj = MF ? (int)blockIdx.y : 0;
   const int fslot = MF ? (P.mf_slot0 + fj) % P.F : 0;
@@ -1163,14 +1091,14 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
   float4* const f_out = MF ? (float4*)P.hist_pix[fslot] : P.out_pix;
   float4* const f_img = MF ? (fj == P.mf_n - 1 ? P.image : nullptr) : P.image;
   const float4* const f_rb = MF ? P.mf_rb + (size_t)fj * 2 * spp : P.rb;
-  const int TP = POOL / spp > 0 ? POOL / spp : 1;
+  const int TP = kPool / spp > 0 ? kPool / spp : 1;
   const int lane = threadIdx.x;
   const int NS = TP * spp;
   // PTW (scenes above kTailMaxObj spheres): the first bounce's pre-test rows one 64-sphere word at a
   // time in LDS, the split tail rounds on the global table, and rand_buffer read from global memory
   // (its LDS copy would not leave room for the rows at 7 waves per SIMD with spp 64)
-  static_assert(!SORT || (LAZY && POOL % 64 == 0 && POOL <= 256), "SORT: hemi is read back from LDS; items are bytes");
-  const BatchLds LO = batch_lds(spp, POOL, 0, !PTW, SORT);
+  static_assert(!SORT || (LAZY && kPool % 64 == 0 && kPool <= 256), "SORT: hemi is read back from LDS; items are bytes");
+  const BatchLds LO = batch_lds<C>(spp, 0);
   char* lbase = (char*)lds;
   float4* prec = (float4*)(lbase + LO.prec);
   float* sres = (float*)(lbase + LO.sres);
@@ -1187,7 +1115,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
   float4* geol = (float4*)(lbase + LO.geol);  // [nobj] when TAIL && nobj <= kTailMaxObj
   // split tail rounds: the sphere table in LDS up to kTailMaxObj spheres; above (TAIL instantiations
   // launched without the LDS table), per-lane reads of the global table (L1/L2-resident)
-  constexpr bool tail_lds = TAIL && PT && !PTW;  // launch_batch: the LDS-table instantiations (<= kTailMaxObj) have PT
+  constexpr bool tail_lds = TAIL && PT && !PTW;  // the LDS-table configurations (<= kTailMaxObj spheres) have PT
   const bool tail_ok = TAIL;
   const float4* const tgeo = tail_lds ? geol : geo;
   // PT: the batched first bounce keeps its per-ray pre-test table in the same LDS rows, so the
@@ -1286,7 +1214,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
   }
   __syncthreads();
   lap(0);
-  if (RT_START_PRIO) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
 
   if (LAZY && ncull == 0) {
     // Empty frustum: every primary ray of the pool provably misses every sphere, so each
@@ -1423,7 +1351,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
     if (ABL == 3) { tsec[6] += (unsigned long long)ncull; tsec[7] += 1; }
     exec_tests += (unsigned long long)ncull;
     if (bitem < total) {
-      if (SORT) bitem = order[bitem];  // the pool's samples in bounce-direction order (RT_B1_SORT)
+      if (SORT) bitem = order[bitem];  // the pool's samples in bounce-direction order
       const int lp = div_spp(bitem), aa = bitem - lp * spp;
       int x, y;
       pool_xy(lp, x, y);
@@ -1522,7 +1450,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
       const unsigned long long lm1 = __ballot(live);
       if (lm1 != 0 && __popcll(lm1) >= P.b1_min) {
         lap(1);
-        if (RT_B1_PRIO) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);  // the batched first bounce at issue priority 1, every other phase at 0
         const ConeB cb = bounce_cone(live, bpos, bdir, lm1);
         float t = -1.0f;
         int ind = -1;
@@ -1540,7 +1468,7 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
           }
           if (acc == 0x123456789abcdefull) b1cost = 1;
         }
-        // RT_B1_DEFER: the exact tests of the survivors whose pre-test passes somewhere are
+        // The exact tests of the survivors whose pre-test passes somewhere are
         // deferred and merged: survivors whose pass masks are disjoint share one exact-test
         // pass, each lane testing the one sphere it passed (ksel, read per lane); a survivor
         // whose mask meets the pending ones first runs them.  Every lane still meets its spheres
@@ -1550,9 +1478,9 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
         unsigned long long ru = 0;  // lanes with a pending sphere (wave-uniform)
         int ksel = 0;               // the pending sphere of each lane in ru
         // the pre-test's direction, NaN on the lanes that are not live (their pre-test then
-        // fails, NaN >= K being false), so the ballot needs no live mask (RT_B1_DEFER)
+        // fails, NaN >= K being false), so the ballot needs no live mask
         f3 tdir = bdir;
-        if (RT_B1_DEFER && !live) tdir = mk(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000), __int_as_float(0x7fc00000));
+        if (!live) tdir = mk(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000), __int_as_float(0x7fc00000));
         auto flush = [&]() {
           const float4 gs = geo[ksel];
           sphere_candidate_if(bpos, bdir, gs, ksel, 0.0001f, t, ind, ru);
@@ -1588,24 +1516,14 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
             // copies it to a VGPR), and the broadcast read waits at once, as the loop would
             int qbase;
             asm("v_mov_b32 %0, %1" : "=v"(qbase) : "s"((int)(size_t)((const char*)qw - lbase)));
-            // (RT_B1_DEFER: the loop on every lane, the live lanes picked by lm1 in the ballots, so
-            // the pending mask stays a scalar value across the loop)
-            if (RT_B1_DEFER || live)
+            // (the loop on every lane, the live lanes picked by lm1 in the ballots, so the pending
+            // mask stays a scalar value across the loop)
+            {
               while (m) {
                 const int j = pop_lowest(m), k = (w << 6) + j;
-#if RT_B1_CREAD
                 // the row read in C from the VGPR row base: one v_lshl_add_u32 for the address, the
                 // compiler's own wait (no inline-asm boundary, whose hazard padding cost an s_nop)
                 const float4 q = *(const float4*)(lbase + (qbase + (j << 4)));
-#else
-                typedef float v4f __attribute__((ext_vector_type(4)));
-                v4f qv;
-                int j_addr_scratch;
-                asm volatile("v_lshl_add_u32 %1, %2, 4, %3\n\tds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-                             : "=v"(qv), "=&v"(j_addr_scratch)
-                             : "s"(j), "v"(qbase));
-                const float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);  // wave-uniform address: LDS broadcast
-#endif
                 const float4 g = gw[j];
                 if (ABL == 7) {  // survivor iterations; with any pre-test pass; with any del >= 0 there
                   const bool pass = fmaf(bdir.z, q.z, fmaf(bdir.y, q.y, bdir.x * q.x)) >= q.w;
@@ -1628,17 +1546,14 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
                   if (i2 == 0x7fffffff) t = t2;
                 }
                 const unsigned long long pm = __builtin_amdgcn_ballot_w64(pass);
-                if (RT_B1_DEFER) {
-                  if (pm != 0) {
-                    if (pm & ru) flush();
-                    ru |= pm;
-                    int kv = k;
-                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(ksel) : "v"(ksel), "v"(kv), "s"(pm));
-                  }
-                } else if (pm != 0) {
-                  sphere_candidate_if(bpos, bdir, g, k, 0.0001f, t, ind, pm);
+                if (pm != 0) {
+                  if (pm & ru) flush();
+                  ru |= pm;
+                  int kv = k;
+                  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(ksel) : "v"(ksel), "v"(kv), "s"(pm));
                 }
               }
+            }
             if (ABL == 6) lap(6);
           } else if (live) {
             while (m) {
@@ -1648,8 +1563,8 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
             }
           }
         }
-        if (RT_B1_DEFER && ru != 0) flush();
-        if (RT_B1_PRIO) __builtin_amdgcn_s_setprio(0);
+        if (ru != 0) flush();
+        __builtin_amdgcn_s_setprio(0);
         if (ABL == 7) { tsec[4] += 1; tsec[5] += (unsigned long long)__popcll(lm1); }
         if (live) {
           if (PL) plane_pass(P, bpos, bdir, 0.0001f, t, ind);
@@ -1670,13 +1585,13 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
   };
 
   if (SORT) {
-    // ---- RT_B1_SORT pre-pass: hemi of every sample into its sres slots, order[] by hemi's octant ---
+    // ---- SORT pre-pass: hemi of every sample into its sres slots, order[] by hemi's octant ---
     // Counting sort over the cells (octant, chunk of 64 items), one cell per lane.  A lane's rank
     // among the chunk's lanes of its octant is a masked popcount of the chunk's three sign ballots;
     // the cell counts are scanned octant by octant (Gray-code order) and chunk by chunk inside an
     // octant, so the order is the same from run to run (items ascending inside an octant).
     // perm[] holds the cell table: it is free until the first prepare().
-    constexpr int NC = POOL / 64, NF = 3;
+    constexpr int NC = kPool / 64, NF = 3;
     static_assert(NC * (1 << NF) <= 64, "one cell per lane");
     const int ln = lane_id_here();
     perm[ln] = 0;
@@ -1909,7 +1824,6 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
       unsigned long long kc = 0;
       for (int c = 0; c < P.ncl; c += 4) {
         const float4 c0 = clus[c], c1 = clus[c + 1], c2 = clus[c + 2], c3 = clus[c + 3];
-#if RT_CL_MASKS
         // (the kept bits by scalar selects: the compiler's (b != 0) | ... << k went through VGPRs)
         const unsigned long long b0 = cluster_may_hit_mask(pos, dir, c0) & hm;
         const unsigned long long b1 = cluster_may_hit_mask(pos, dir, c1) & hm;
@@ -1920,13 +1834,6 @@ __global__ __launch_bounds__(64, MINW) void ao_batch_kernel(FrameParams P, const
         unsigned nib = (b0 ? 16u : 0u) | (b1 ? 32u : 0u) | (b2 ? 64u : 0u) | (b3 ? 128u : 0u);
         asm("" : "+s"(nib));
         kc |= (unsigned long long)(nib >> 4) << c;
-#else
-        const unsigned long long b0 = __builtin_amdgcn_ballot_w64(cluster_may_hit(pos, dir, c0)) & hm;
-        const unsigned long long b1 = __builtin_amdgcn_ballot_w64(cluster_may_hit(pos, dir, c1)) & hm;
-        const unsigned long long b2 = __builtin_amdgcn_ballot_w64(cluster_may_hit(pos, dir, c2)) & hm;
-        const unsigned long long b3 = __builtin_amdgcn_ballot_w64(cluster_may_hit(pos, dir, c3)) & hm;
-        kc |= (unsigned long long)((b0 != 0) | (b1 != 0) << 1 | (b2 != 0) << 2 | (b3 != 0) << 3) << c;
-#endif
       }
       // (bits of the slots past ncl need no mask: their member words are zero, rt_shim build_clusters)
       float t = -1.0f;
@@ -2361,7 +2268,7 @@ __global__ void selftest_kernel(int fn, const float* __restrict__ in, float* __r
       const f3 lv = mk(in[4 * i], in[4 * i + 1], in[4 * i + 2]);
       const f3 l = normalize(lv);
       const float len = sqrtf(dot(lv, lv));
-      const bool occ = shadow_occludes(in[4 * i + 3], l, (double)len, shadow_bounds(l, len));
+      const bool occ = shadow_occludes(in[4 * i + 3], l, (double)len);
       out[5 * i] = l.x; out[5 * i + 1] = l.y; out[5 * i + 2] = l.z; out[5 * i + 3] = len;
       out[5 * i + 4] = occ ? 1.0f : 0.0f;
       break;
@@ -2385,37 +2292,108 @@ size_t tab_lds_bytes(const FrameParams& p) { return (size_t)5 * (p.nobj > 0 ? p.
 
 }  // namespace
 
-// The production pooled AO kernel: split tail rounds and the per-ray first-bounce pre-test when
-// the sphere table fits in LDS (tl), with or without the work counters (cnt), with or without
-// planes (PL).
 constexpr int kRefDepth = 20;  // RECURSION_DEPTH, ao_compute.glsl:9
-// RT_B1_SORT: least spheres of a scene whose pools are sorted (RT_B1_SORT_MIN overrides: A/B builds)
+// least spheres of a scene whose pools are sorted (RT_B1_SORT_MIN overrides: A/B builds)
 #ifndef RT_B1_SORT_MIN
 #define RT_B1_SORT_MIN 48
 #endif
 constexpr int kB1SortMinObj = RT_B1_SORT_MIN;
 
-template <int SPPC, bool PL, int DC = 0, bool CLON = false, bool SORT = false>
-inline void launch_batch(bool tl, bool cnt, dim3 g, dim3 b, size_t lds, hipStream_t stream, const FrameParams& q) {
-  constexpr bool GT = RT_GLOBAL_TAIL;  // split tail rounds above kTailMaxObj spheres (global table)
-  constexpr bool TLC = RT_TL_CLUSTERS;  // the cluster cull in the LDS-table (<= kTailMaxObj) instantiations
-  constexpr bool PTWV = RT_PT_WIDE;     // above kTailMaxObj spheres: the pre-test rows word by word
-  if (q.mf_n > 0) {  // multi-frame mode-2 launch (never with counters: rt_compute_frames checks)
-    g.y = (unsigned)q.mf_n;
-    if (tl)
-      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, true, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
-    else
-      hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, true, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
-    return;
+// The production AO configuration of a launch: AoProd<sppc, dc, flags>.
+struct AoChoice {
+  int sppc, dc;
+  unsigned flags;  // AO_*
+};
+constexpr bool operator==(const AoChoice& a, const AoChoice& b) {
+  return a.sppc == b.sppc && a.dc == b.dc && a.flags == b.flags;
+}
+// - spp 4 (the reference's AA), 16 (configs c/d) and 64 (config e; not with planes) have their own
+//   instantiations: constant LDS offsets and it / spp, fewer scalar registers.
+// - The reference's RECURSION_DEPTH with bounce-ray clusters (every all-sphere scene of 16..256
+//   spheres) also has its own for spp 16 and 64: with the depth a constant and the rounds' plain
+//   full-scan fallback compiled out, fewer scalar registers are spilled to vector lanes (each
+//   reload is a v_readlane on the bounce rounds' path).
+// - The pools are sorted in scenes without planes of at least kB1SortMinObj spheres (below, the
+//   first bounce's cone keeps too few spheres for the sort to pay: 1920x1080, 16 spp, sorted
+//   against unsorted +2.5% / +2% / +4% at 16 / 24 / 32 spheres, -2% at 48,
+//   profiles/r07_ab_b1_sort_threshold.txt; plane scenes were not measured and stay unsorted).
+// - Above kTailMaxObj spheres the sphere table does not fit the kernel's LDS rows (AO_WIDE).
+// - Timed launches pass no counters: the counter code is compiled out.  A multi-frame launch
+//   never has counters (rt_compute_frames checks).
+constexpr AoChoice ao_select(int spp, int D, int ncl, int nobj, int nplanes, bool counters, bool multi_frame) {
+  const bool pl = nplanes > 0;
+  const bool own = spp == 16 || spp == 4 || (spp == 64 && !pl);
+  const bool clon = !pl && (spp == 16 || spp == 64) && D == kRefDepth && ncl > 0;
+  return AoChoice{own ? spp : 0, clon ? kRefDepth : 0,
+                  (pl ? AO_PL : 0u) | (clon ? AO_CLON : 0u) | (RT_B1_SORT && !pl && nobj >= kB1SortMinObj ? AO_SORT : 0u) |
+                      (nobj > kTailMaxObj ? AO_WIDE : 0u) | (multi_frame ? AO_MF : counters ? AO_CNT : 0u)};
+}
+// The dispatch's regression test (derived from the launcher this function replaced).  Arguments:
+// spp, D, ncl, nobj, nplanes, counters, multi-frame.
+constexpr unsigned kSortBit = RT_B1_SORT ? AO_SORT : 0u;
+// bench.py's configs, timed launch; (a) and (b) are Phong / hybrid scenes, never launched as AO
+static_assert(ao_select(1, 20, 0, 4, 0, false, false) == AoChoice{0, 0, 0}, "a");
+static_assert(ao_select(1, 20, 4, 16, 0, false, false) == AoChoice{0, 0, 0}, "b");
+static_assert(ao_select(16, 20, 8, 64, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "c");
+static_assert(ao_select(16, 20, 8, 64, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "d");
+static_assert(ao_select(64, 20, 16, 256, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "e");
+static_assert(ao_select(16, 20, 9, 65, 1, false, false) == AoChoice{16, 0, AO_PL}, "p");
+static_assert(ao_select(16, 20, 9, 65, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "q");
+static_assert(ao_select(16, 20, 0, 10, 1, false, false) == AoChoice{16, 0, AO_PL}, "s1");
+static_assert(ao_select(4, 20, 0, 10, 1, false, false) == AoChoice{4, 0, AO_PL}, "ref");
+// counters on; a multi-frame launch (its counters flag is ignored)
+static_assert(ao_select(16, 20, 8, 64, 0, true, false) == AoChoice{16, 20, AO_CLON | kSortBit | AO_CNT}, "counters");
+static_assert(ao_select(16, 20, 8, 64, 0, false, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
+static_assert(ao_select(16, 20, 8, 64, 0, true, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
+// just under and at kB1SortMinObj; at and above kTailMaxObj
+static_assert(ao_select(16, 20, 6, kB1SortMinObj - 1, 0, false, false) == AoChoice{16, 20, AO_CLON}, "unsorted");
+static_assert(ao_select(16, 20, 6, kB1SortMinObj, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "sorted");
+static_assert(ao_select(64, 20, 12, kTailMaxObj, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit}, "LDS table");
+static_assert(ao_select(64, 20, 12, kTailMaxObj + 1, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "wide");
+// another depth, no clusters, other spp, planes with spp 64
+static_assert(ao_select(16, 10, 8, 64, 0, false, false) == AoChoice{16, 0, kSortBit}, "depth 10");
+static_assert(ao_select(64, 20, 0, 300, 0, false, false) == AoChoice{64, 0, kSortBit | AO_WIDE}, "no clusters");
+static_assert(ao_select(4, 20, 8, 64, 0, false, false) == AoChoice{4, 0, kSortBit}, "spp 4");
+static_assert(ao_select(8, 20, 8, 64, 0, true, false) == AoChoice{0, 0, kSortBit | AO_CNT}, "spp 8");
+static_assert(ao_select(64, 20, 8, 200, 2, false, false) == AoChoice{0, 0, AO_PL | AO_WIDE}, "planes, spp 64");
+
+// Launch ao_batch_kernel<C> over `pools` pools: the LDS rows after the layout hold the sphere
+// table (C::PTW: one 64-sphere word of pre-test rows)
+template <class C>
+inline void launch_ao(long long pools, hipStream_t stream, const FrameParams& q) {
+  const dim3 g((unsigned)pools, C::MF ? (unsigned)q.mf_n : 1u);
+  hipLaunchKernelGGL((ao_batch_kernel<C>), g, dim3(64), (size_t)batch_lds<C>(q.spp, C::PTW ? 64 : q.nobj).total, stream,
+                     q, q.sph);
+}
+// AoChoice -> AoProd: the library holds exactly the configurations ao_select can return
+template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT
+inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
+  switch (flags & (AO_WIDE | AO_CNT | AO_MF)) {
+    case 0: return launch_ao<AoProd<SPPC, DC, SHAPE>>(pools, stream, q);
+    case AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_CNT>>(pools, stream, q);
+    case AO_MF: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_MF>>(pools, stream, q);
+    case AO_WIDE: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE>>(pools, stream, q);
+    case AO_WIDE | AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_CNT>>(pools, stream, q);
+    case AO_WIDE | AO_MF: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_MF>>(pools, stream, q);
   }
-  if (tl && cnt)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, true, PL, false, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
-  else if (tl)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, true, true, SPPC, true, false, PL, false, TLC, DC, CLON, false, SORT>), g, b, lds, stream, q, q.sph);
-  else if (cnt)
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, true, PL, false, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
-  else
-    hipLaunchKernelGGL((ao_batch_kernel<kAoMinWaves, true, kPool, 0, GT, true, SPPC, PTWV, false, PL, false, true, DC, CLON, PTWV, SORT>), g, b, lds, stream, q, q.sph);
+}
+template <unsigned SORT>  // 0 or AO_SORT
+inline void launch_ao_choice(const AoChoice& c, long long pools, hipStream_t stream, const FrameParams& q) {
+  if (c.flags & AO_PL) {
+    if constexpr (SORT == 0) {
+      if (c.sppc == 16) launch_ao_shape<16, 0, AO_PL>(c.flags, pools, stream, q);
+      else if (c.sppc == 4) launch_ao_shape<4, 0, AO_PL>(c.flags, pools, stream, q);
+      else launch_ao_shape<0, 0, AO_PL>(c.flags, pools, stream, q);
+    }
+  } else if (c.flags & AO_CLON) {
+    if (c.sppc == 16) launch_ao_shape<16, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q);
+    else launch_ao_shape<64, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q);
+  } else {
+    if (c.sppc == 16) launch_ao_shape<16, 0, SORT>(c.flags, pools, stream, q);
+    else if (c.sppc == 64) launch_ao_shape<64, 0, SORT>(c.flags, pools, stream, q);
+    else if (c.sppc == 4) launch_ao_shape<4, 0, SORT>(c.flags, pools, stream, q);
+    else launch_ao_shape<0, 0, SORT>(c.flags, pools, stream, q);
+  }
 }
 
 // g-buffer layout conversion (rt_download / rt_upload_gbuffer, the host-buffer path of
@@ -2441,7 +2419,7 @@ __global__ __launch_bounds__(256) void gbuf_convert_kernel(GbufXfer x) {
   }
 }
 
-inline hipError_t launch_gbuf_convert_impl(const GbufXfer& x, hipStream_t stream) {
+hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream) {
   const size_t total = (size_t)x.F * x.W * x.R;
   if (total == 0) return hipSuccess;
   hipLaunchKernelGGL(gbuf_convert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x);
@@ -2489,83 +2467,32 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const long long npix = (long long)p.trace_rows * p.W;
     const int TP = kPool / p.spp > 0 ? kPool / p.spp : 1;
     const long long pools = (npix + TP - 1) / TP;
-    const bool tl = p.nobj <= kTailMaxObj;
-    // RT_B1_SORT: scenes without planes of at least kB1SortMinObj spheres (below, the first bounce's
-    // cone keeps too few spheres for the sort to pay: 1920x1080, 16 spp, sorted against unsorted
-    // +2.5% / +2% / +4% at 16 / 24 / 32 spheres, -2% at 48, profiles/r07_ab_b1_sort_threshold.txt;
-    // plane scenes were not measured and stay unsorted)
-    const bool sort = RT_B1_SORT && !pl && p.nobj >= kB1SortMinObj;
-    const size_t psh =
-        (size_t)batch_lds(p.spp, kPool, tl ? p.nobj : (RT_PT_WIDE ? 64 : 0), tl || !RT_PT_WIDE, sort).total;
-    const dim3 g((unsigned)pools), b(64);
-    // timed launches pass no counters: the counter code is compiled out (fewer live scalars)
-    const bool cnt = p.counters || p.row_counters;
-    // spp 4 (the reference's AA), 16 (configs c/d) and 64 (config e) have their own
-    // instantiations: constant LDS offsets and it / spp, fewer scalar registers
-    // The reference's RECURSION_DEPTH (20, ao_compute.glsl:9) with bounce-ray clusters (every
-    // scene of 16..256 spheres) also has its own instantiations for spp 16 and 64: with the depth
-    // a constant and the rounds' plain full-scan fallback compiled out, fewer scalar registers are
-    // spilled to vector lanes (each reload is a v_readlane on the bounce rounds' path)
-    if (sort) {
-      const bool ref_d = p.D == kRefDepth && p.ncl > 0;
-      if (p.spp == 16 && ref_d) launch_batch<16, false, kRefDepth, true, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 64 && ref_d) launch_batch<64, false, kRefDepth, true, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 16) launch_batch<16, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 64) launch_batch<64, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 4) launch_batch<4, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-      else launch_batch<0, false, 0, false, RT_B1_SORT != 0>(tl, cnt, g, b, psh, stream, q);
-    } else if (!pl) {
-      const bool ref_d = p.D == kRefDepth && p.ncl > 0;
-      if (p.spp == 16 && ref_d) launch_batch<16, false, kRefDepth, true>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 64 && ref_d) launch_batch<64, false, kRefDepth, true>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 16) launch_batch<16, false>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 64) launch_batch<64, false>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 4) launch_batch<4, false>(tl, cnt, g, b, psh, stream, q);
-      else launch_batch<0, false>(tl, cnt, g, b, psh, stream, q);
-    } else {
-      if (p.spp == 16) launch_batch<16, true>(tl, cnt, g, b, psh, stream, q);
-      else if (p.spp == 4) launch_batch<4, true>(tl, cnt, g, b, psh, stream, q);
-      else launch_batch<0, true>(tl, cnt, g, b, psh, stream, q);
-    }
+    const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.counters || p.row_counters, p.mf_n > 0);
+    // (kSortBit: a build with RT_B1_SORT=0 never selects the sort and compiles no SORT instantiation)
+    if (c.flags & AO_SORT) launch_ao_choice<kSortBit>(c, pools, stream, q);
+    else launch_ao_choice<0>(c, pools, stream, q);
     return hipGetLastError();
   }
   // modes 3/4 multi-frame launches: FPB frames per block (block_frames)
   const int fpb = program == K_PHONG ? kPhongFramesPerBlock : kHybridFramesPerBlock;
-  const int tpb = program == K_HYBRID ? kHybridTilesPerBlock : 1;
   // hybrid blocks: kHyBW x kHyBW waves of 8x8 pixels (kHyTile = 8 kHyBW px); phong: 2x2 waves
   const int tw = program == K_HYBRID ? kHyTile : 16;
-  dim3 grid((p.W + tw - 1) / tw, ((p.trace_rows + tw - 1) / tw + tpb - 1) / tpb, p.mf_n > 0 ? (p.mf_n + fpb - 1) / fpb : 1);
+  dim3 grid((p.W + tw - 1) / tw, (p.trace_rows + tw - 1) / tw, p.mf_n > 0 ? (p.mf_n + fpb - 1) / fpb : 1);
   const dim3 hyb(64 * kHyBW * kHyBW);
-  // scenes of at most kTabLdsMax objects: the tables staged in LDS per wave (LT)
-// Modes 3/4 read the shape tables through the caches (scalar loads for the wave-uniform culls
-// and survivor tests, vector loads for the hit's material) instead of staging them in LDS per
-// block: no staging round trip and no block barrier before a wave's first test.  Round 5,
-// burst A/Bs: hybrid (b) 28.15 -> 26.78 us per launch (-4.9%), phong (a) 6.87 -> 6.75 us
-// (-1.7%), bit-identical (profiles/r05n_*).  Round 2 had measured the LDS tables faster
-// (40.4 -> 37.9 us) on the kernels of that time.  0 restores the LDS tables (A/B builds).
-#ifndef RT_HY_NOLT
-#define RT_HY_NOLT 1
-#endif
-#ifndef RT_PH_NOLT
-#define RT_PH_NOLT 1
-#endif
-  const bool lt = p.nobj <= kTabLdsMax && !(RT_HY_NOLT && program == K_HYBRID) && !(RT_PH_NOLT && program == K_PHONG);
-  const size_t ltb = lt ? tab_lds_bytes(p) : 0;
+  // The shape tables are read through the caches (scalar loads for the wave-uniform culls and
+  // survivor tests, vector loads for the hit's material), not staged in LDS per block (the LT
+  // instantiations, A/B tools library only)
   const bool mf = p.mf_n > 0;  // multi-frame launch; single-frame ones take the MF = false kernels
   switch (program) {
     case K_PHONG:
-      if (pl && lt) hipLaunchKernelGGL((phong_kernel<true, true, true>), grid, dim3(kBlock), ltb, stream, q.sph, q.shapes, q);
-      else if (pl && mf) hipLaunchKernelGGL((phong_kernel<true, true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      if (pl && mf) hipLaunchKernelGGL((phong_kernel<true, true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
       else if (pl) hipLaunchKernelGGL((phong_kernel<true, true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (lt) hipLaunchKernelGGL((phong_kernel<true, false, true>), grid, dim3(kBlock), ltb, stream, q.sph, q.shapes, q);
       else if (mf) hipLaunchKernelGGL((phong_kernel<true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
       else hipLaunchKernelGGL((phong_kernel<true, false, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
       break;
     case K_HYBRID:
-      if (pl && lt) hipLaunchKernelGGL((hybrid_kernel<true, true, true, 0, kHyBW, kHyBW>), grid, hyb, ltb, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (pl && mf) hipLaunchKernelGGL((hybrid_kernel<true, true, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      if (pl && mf) hipLaunchKernelGGL((hybrid_kernel<true, true, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
       else if (pl) hipLaunchKernelGGL((hybrid_kernel<true, true, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (lt) hipLaunchKernelGGL((hybrid_kernel<true, false, true, 0, kHyBW, kHyBW>), grid, hyb, ltb, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
       else if (mf) hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
       else hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
       break;
@@ -2580,7 +2507,7 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
   return hipGetLastError();
 }
 
-inline hipError_t launch_selftest_impl(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream) {
+hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(selftest_kernel, dim3(grid), dim3(256), 0, stream, fn, d_in, d_out, n);

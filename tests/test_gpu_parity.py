@@ -153,7 +153,8 @@ def test_ao_spp_variants(spp, scene):
 def test_ao_scene_sizes(nobj):
     """Sphere counts around the kernel's 64-sphere words and the 128-object LDS table limit
     (split tail rounds + the first bounce's per-ray pre-test table up to 128; above, the pre-test
-    rows one word at a time with rand_buffer read from global memory, RT_PT_WIDE); "p": plus a
+    rows one word at a time with rand_buffer read from global memory; that switch, RT_PT_WIDE, was
+    retired and the kernel now always does this); "p": plus a
     ground plane (the plane-testing instantiations, with and without the LDS table); "@n": n spp
     (the spp 4 and 64 instantiations; 16 otherwise)."""
     W, H = 48, 32
@@ -345,11 +346,10 @@ def _shadow_occludes_b64(l, ln, t):
 
 def test_shadow_occluder_decision():
     """The production kernels decide every shadow occluder test with the binary64 sequence
-    (RT_SHADOW_FAST = 0, rt_kernels_impl.h: shadow_bounds gives {0, inf}, so no decision is taken
-    in float).  Its decision equals the binary64 sequence evaluated exactly on t drawn at and
-    around len (1 -+ 2^-12) (the float fast path's bounds, kept as probe points), around len
-    itself, and for degenerate light vectors (zero, tiny, huge).  The float fast path is an A/B
-    variant only and is not compiled into librtrt.so."""
+    (rt_kernels_impl.h shadow_occludes: no decision is taken in float; the RT_SHADOW_FAST switch
+    and its float bounds were retired).  Its decision equals the binary64 sequence evaluated
+    exactly on t drawn at and around len (1 -+ 2^-12) (the retired float path's bounds, kept as
+    probe points), around len itself, and for degenerate light vectors (zero, tiny, huge)."""
     r = Renderer(8, 8, 1, 1)
     rng = np.random.default_rng(11)
     n = 6000

@@ -145,6 +145,22 @@ __global__ __launch_bounds__(kBlock) void ao_kernel(FrameParams P, const float4*
 
 }  // namespace
 
+// The AO variants' configurations: a production configuration (AoProd) or the defaults
+// (AoConfig) with members overridden by name.
+using ProdD = AoProd<16, kRefDepth, AO_CLON>;                        // config (d), timed, unsorted
+using ProdECounted = AoProd<64, kRefDepth, AO_CLON | AO_WIDE | AO_CNT>;  // config (e) with counters, unsorted
+using Counted16 = AoProd<16, 0, AO_CNT>;                            // spp 16, any depth, with counters
+using Counted16Sorted = AoProd<16, 0, AO_CNT | AO_SORT>;
+using PlaneCounted16 = AoProd<16, 0, AO_PL | AO_CNT>;
+struct NoPretest : AoProd<16, 0, 0> { static constexpr bool PT = false; };
+struct NoLazy : AoConfig { static constexpr bool LAZY = false; };
+struct NoFirstBounce : AoConfig { static constexpr bool TAIL = true; };  // (so no pre-test: the table stays in the LDS rows' place)
+struct NoTail : AoConfig { static constexpr bool B1 = true; };
+struct TailNoPretest : NoTail { static constexpr bool TAIL = true; };
+struct PlaneNoTail : NoTail { static constexpr bool PL = true; };
+template <class B, int A>
+struct Abl : B { static constexpr int ABL = A; };  // B with diagnostic A (ao_batch_kernel's ABL)
+
 // ---- A/B build only (make ablib -> build/librtrt_ab.so; tools/ab.py, tools/sections.py) -----
 // RTRT_AO_VARIANT selects an experimental AO kernel per launch: 9 (no first-bounce pre-test),
 // 27 (no batched first bounce), 17 (no split tail rounds), 11 (no lazy shortcuts), 91-93 (timing
@@ -178,69 +194,68 @@ static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t strea
     return true;
   }
   if (variant == 7 || (p.nplanes > 0 && variant != 93)) return false;  // production
+  // every variant's LDS rows after the layout: ntail float4 (the sphere table where the variant stages it)
+  auto go = [&](auto cfg, int ntail) {
+    using C = decltype(cfg);
+    hipLaunchKernelGGL((ao_batch_kernel<C>), g, b, (size_t)batch_lds<C>(p.spp, ntail).total, stream, q, q.sph);
+  };
   if (variant == 93 && p.nplanes > 0) {  // section clocks of the production plane kernel
-    const size_t pl_sh = (size_t)batch_lds(p.spp, kPool, tl ? p.nobj : 0).total;
-    if (tl && p.spp == 16)
-      hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, true, true, 16, true, true, true>), g, b, pl_sh, stream, q, q.sph);
-    else
-      hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, false, true, 0, false, true, true>), g, b, pl_sh, stream, q, q.sph);
+    if (tl && p.spp == 16) go(Abl<PlaneCounted16, 3>{}, p.nobj);
+    else go(Abl<PlaneNoTail, 3>{}, tl ? p.nobj : 0);
     return true;
   }
-  const size_t psh = (size_t)batch_lds(p.spp, kPool, (variant == 9 || variant == 27 || variant >= 93) && tl ? p.nobj : 0).total;
+  const int ntail = (variant == 9 || variant == 27 || variant >= 93) && tl ? p.nobj : 0;
   if (variant == 9 && p.spp == 16 && tl)  // 7 without the per-ray first-bounce pre-test
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 0, true, true, 16, false, false>), g, b, psh, stream, q, q.sph);
+    go(NoPretest{}, ntail);
   else if (variant == 27 && tl)  // 7 without the batched first bounce
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 0, true>), g, b, psh, stream, q, q.sph);
+    go(NoFirstBounce{}, ntail);
   else if (variant == 11)
-    hipLaunchKernelGGL((ao_batch_kernel<7, false>), g, b, psh, stream, q, q.sph);
+    go(NoLazy{}, ntail);
   else if (variant >= 101 && variant <= 110 && tl && p.spp == 16 && p.nplanes == 0 && q.ncl > 0) {
     // instruction budget (tools/sq_budget.sh): the production (d) instantiation (no counters,
     // depth 20, clusters) and its ablations, each repeating one section's work once more:
     // 101 none, 102 cluster-round tests (ABL 1), 103 culled primary tests (ABL 2), 104 the five
     // hashes (ABL 4), 105 first-bounce survivor iterations (ABL 5)
-    const size_t ps = (size_t)batch_lds(16, kPool, p.nobj).total;
-    if (variant == 101) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 0, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 102) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 1, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 103) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 2, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 104) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 4, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 105) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 5, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
+    if (variant == 101) go(ProdD{}, p.nobj);
+    if (variant == 102) go(Abl<ProdD, 1>{}, p.nobj);
+    if (variant == 103) go(Abl<ProdD, 2>{}, p.nobj);
+    if (variant == 104) go(Abl<ProdD, 4>{}, p.nobj);
+    if (variant == 105) go(Abl<ProdD, 5>{}, p.nobj);
     // round 6: 106 the hit shading's arithmetic (ABL 9), 107 the primary setup after the hashes
     // (ABL 10), 108 the hand-out shuffles (ABL 11), 109 the first bounce's cone + cull (ABL 12),
     // 110 the full rounds' cluster cull (ABL 13)
-    if (variant == 106) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 9, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 107) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 10, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 108) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 11, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 109) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 12, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
-    if (variant == 110) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 13, true, true, 16, true, false, false, false, true, 20, true>), g, b, ps, stream, q, q.sph);
+    if (variant == 106) go(Abl<ProdD, 9>{}, p.nobj);
+    if (variant == 107) go(Abl<ProdD, 10>{}, p.nobj);
+    if (variant == 108) go(Abl<ProdD, 11>{}, p.nobj);
+    if (variant == 109) go(Abl<ProdD, 12>{}, p.nobj);
+    if (variant == 110) go(Abl<ProdD, 13>{}, p.nobj);
   } else if ((variant == 193 || variant == 196 || variant == 198) && !tl && p.spp == 64 && p.nplanes == 0 &&
              q.ncl > 0 && p.D == 20) {
     // section clocks of config (e)'s production instantiation (above kTailMaxObj spheres: the
     // word-by-word pre-test, rand_buffer from global memory): 193 as 93, 196 as 96, 198 as 98
-    const size_t pw = (size_t)batch_lds(64, kPool, 64, false).total;
-    if (variant == 193) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, true, true, 64, true, true, false, false, true, 20, true, true>), g, b, pw, stream, q, q.sph);
-    if (variant == 196) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 6, true, true, 64, true, true, false, false, true, 20, true, true>), g, b, pw, stream, q, q.sph);
-    if (variant == 198) hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 8, true, true, 64, true, true, false, false, true, 20, true, true>), g, b, pw, stream, q, q.sph);
+    if (variant == 193) go(Abl<ProdECounted, 3>{}, 64);
+    if (variant == 196) go(Abl<ProdECounted, 6>{}, 64);
+    if (variant == 198) go(Abl<ProdECounted, 8>{}, 64);
   } else if (variant == 91)
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 1>), g, b, psh, stream, q, q.sph);
+    go(Abl<AoConfig, 1>{}, ntail);
   else if (variant == 92)
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 2>), g, b, psh, stream, q, q.sph);
+    go(Abl<AoConfig, 2>{}, ntail);
   else if (variant == 96 && tl && p.spp == 16)  // section clocks, first bounce split in 3
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 6, true, true, 16, true>), g, b, psh, stream, q, q.sph);
+    go(Abl<Counted16, 6>{}, ntail);
   else if (variant == 98 && tl && p.spp == 16)  // section clocks, split tail rounds apart from full rounds
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 8, true, true, 16, true>), g, b, psh, stream, q, q.sph);
+    go(Abl<Counted16, 8>{}, ntail);
   else if (variant == 97 && tl && p.spp == 16)  // first-bounce / bounce-round event counts
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 7, true, true, 16, true>), g, b, psh, stream, q, q.sph);
-  else if (variant == 197 && tl && p.spp == 16)  // 97 with the pool's samples sorted by hemi's octant (RT_B1_SORT)
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 7, true, true, 16, true, true, false, false, true, 0, false, false, true>), g, b,
-                       (size_t)batch_lds(16, kPool, p.nobj, true, true).total, stream, q, q.sph);
+    go(Abl<Counted16, 7>{}, ntail);
+  else if (variant == 197 && tl && p.spp == 16)  // 97 with the pool's samples sorted by hemi's octant (AoConfig::SORT)
+    go(Abl<Counted16Sorted, 7>{}, p.nobj);
   else if (variant == 93 && tl && p.spp == 16)  // section clocks of the production kernel
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, true, true, 16, true>), g, b, psh, stream, q, q.sph);
+    go(Abl<Counted16, 3>{}, ntail);
   else if (variant == 93 && tl)
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, true, true>), g, b, psh, stream, q, q.sph);
+    go(Abl<TailNoPretest, 3>{}, ntail);
   else if (variant == 93)
-    hipLaunchKernelGGL((ao_batch_kernel<7, true, kPool, 3, false, true>), g, b, psh, stream, q, q.sph);
+    go(Abl<NoTail, 3>{}, ntail);
   else  // 17: without the split tail rounds
-    hipLaunchKernelGGL(ao_batch_kernel<7>, g, b, psh, stream, q, q.sph);
+    go(AoConfig{}, ntail);
   return true;
 }
 static bool ab_general() {
@@ -286,7 +301,7 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream)
       q.tile_order = nullptr;
       q.tile_cost = nullptr;
     }
-    // (tables through the caches, as production since round 5: RT_HY_NOLT)
+    // (tables through the caches, as production since round 5)
     if (k == 11) hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, 1, 1>), gr(1, 1), dim3(64), 0, stream, q.tile_order, q.sph, q.shapes, gr(1, 1).x, q);
     else if (k == 21) hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, 2, 1>), gr(2, 1), dim3(128), 0, stream, q.tile_order, q.sph, q.shapes, gr(2, 1).x, q);
     else if (k == 41) hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, 4, 1>), gr(4, 1), dim3(256), 0, stream, q.tile_order, q.sph, q.shapes, gr(4, 1).x, q);
@@ -303,11 +318,5 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream)
   }
   return launch_production(program, p, q, stream);
 }
-
-hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream) {
-  return launch_selftest_impl(fn, d_in, d_out, n, stream);
-}
-
-hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream) { return launch_gbuf_convert_impl(x, stream); }
 
 }  // namespace rt

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # round 6 GPU job t: config (e) (256 spheres) with the first bounce's pre-test rows one word at a
-# time (RT_PT_WIDE=1) and with clusters of 16: per-launch A/B (images must be bit-identical), then
+# time (RT_PT_WIDE=1, a switch since retired: the kernel always does this) and with clusters of 16: per-launch A/B (images must be bit-identical), then
 # the whole (e) frame against the oracle on the pre-test build
 set -uo pipefail
 O=gpurun_out/r06t; mkdir -p $O
