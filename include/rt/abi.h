@@ -153,6 +153,25 @@ int rt_tile_schedule_state(rt_ctx* ctx);
 /* how many longest-first orders have been taken up since the schedule was (re)enabled: each new
  * order replaces a table that launches still in flight may read, so tests count the swaps */
 int rt_tile_schedule_orders(rt_ctx* ctx);
+/* Cull cache of the AO programs (modes 1 and 2), on by default.  Every pool of an AO launch starts
+ * by culling the sphere table against the cone of its primary rays; that cull reads the camera,
+ * the frame and strip geometry, spp, int(mode.z) and the sphere rows, none of which the render
+ * loop's per-frame update changes (src/main.cpp:763-781 replaces rand_buffer and mode.y).  Once two
+ * launches in a row have repeated the previous launch's values of those inputs (compared byte for
+ * byte on the host), the pools' masks are written to a device table once and the launches load
+ * them, until a launch's inputs differ: that launch and the next run the in-kernel cull again.  A
+ * camera that moves every frame never builds a table.  Scenes with planes, and contexts whose
+ * table would exceed 512 MiB or could not be allocated, always cull in the kernel.  Images, g-buffers
+ * and work counters are bit-identical either way.  on = 0: every launch culls in the kernel. */
+int rt_set_cull_cache(rt_ctx* ctx, int on);
+/* Table fills and AO launches that loaded their masks since rt_create, and the table's bytes
+ * (0 until the first fill).  Any pointer may be NULL. */
+int rt_cull_cache_stats(rt_ctx* ctx, long long* fills, long long* cached_launches, size_t* table_bytes);
+/* The cull cache's key of `header` (rt_header_bytes(num_shapes, spp) bytes) for a context created
+ * with `cfg`: written to `key` when it fits in key_cap bytes (key may be NULL).  Returns the key's
+ * size in bytes, 0 for an invalid configuration or header.  Two launches share a table iff their
+ * keys are equal.  Never touches the GPU. */
+size_t rt_cull_key(const rt_config* cfg, const void* header, size_t header_bytes, void* key, size_t key_cap);
 /* Copy device state to the host in the REFERENCE layout.  Any pointer may be NULL.
  * pixels/normals/depth: [F][W][R] vec4 (x-major, y fastest; R = rows of this context),
  * image: [R][W] rgba32f (row 0 = row_begin, bottom-left origin like the GL texture). */

@@ -61,6 +61,9 @@ SIGNATURES = {
     "rt_set_tile_schedule": (C.c_int, [_ctx, C.c_int]),
     "rt_tile_schedule_state": (C.c_int, [_ctx]),
     "rt_tile_schedule_orders": (C.c_int, [_ctx]),
+    "rt_set_cull_cache": (C.c_int, [_ctx, C.c_int]),
+    "rt_cull_cache_stats": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]),
+    "rt_cull_key": (C.c_size_t, [C.POINTER(rt_config), _vp, C.c_size_t, _vp, C.c_size_t]),
     "rt_download": (C.c_int, [_ctx, _fp, _fp, _fp, _fp]),
     "rt_download_rect": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     "rt_upload_gbuffer": (C.c_int, [_ctx, _fp, _fp, _fp]),

@@ -89,7 +89,18 @@ struct FrameParams {
   // stores its bounce-round count at tile_cost[tile * 4 + wave] when non-null
   const unsigned* tile_order;
   unsigned* tile_cost;
+  // AO, all-sphere scenes: the pools' primary-ray cull masks, [pools][(nobj + 63) / 64] u64 as
+  // launch_cull_fill wrote them for this camera, scene and strip; non-null selects the kernels
+  // that load their pool's masks instead of computing them (nullptr: the in-kernel cull)
+  const unsigned long long* cull;
 };
+
+// AO pools: kAoPool samples each, i.e. max(1, kAoPool / spp) consecutive pixels of the launch's rows
+constexpr int kAoPool = 256;
+constexpr long long ao_pool_count(int trace_rows, int W, int spp) {
+  const int TP = kAoPool / spp > 0 ? kAoPool / spp : 1;
+  return ((long long)trace_rows * W + TP - 1) / TP;
+}
 
 // Bounce-ray cluster culling (AO later bounce rounds): at most kMaxClusters clusters (a wave-uniform
 // u64 of kept clusters), member masks over the first kClusterWords * 64 spheres.
@@ -123,6 +134,12 @@ enum KernelId { K_AOP = 1, K_POST = 2, K_AO = 3, K_PHONG = 4, K_HYBRID = 5 };
 // hit (eval_ray returns -1 for it, p_compute.glsl:121-138) and is skipped through the NaN
 // entries of the sphere table.  Returns hipSuccess or the launch error.
 hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream);
+
+// Fill `table` ([ao_pool_count(p.trace_rows, p.W, p.spp)][(p.nobj + 63) / 64] u64) with the
+// primary-ray cull masks an AO launch of p computes per pool: the same device functions on the same
+// operands, so a launch that reads them through FrameParams::cull renders what it would have.
+// They depend on p's camera, frame and strip geometry, spp, nobj and sphere rows only.
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, hipStream_t stream);
 
 // g-buffer layout conversion between the reference's [F][W][R] vec4 (x-major, y fastest:
 // src/main.cpp:49-85 over a context's R rows) and the device slots of one array kind (0 pixels:

@@ -239,7 +239,7 @@ __device__ __forceinline__ int block_frames(const FrameParams& P, int& j0) {
 // never accepted) and is skipped.
 // ---------------------------------------------------------------------------------------
 constexpr float kInv6 = 1.0f / 6.0f;  // correctly rounded (div_rn_by)
-constexpr int kPool = 256;
+constexpr int kPool = kAoPool;
 constexpr int kSetupCost = 24;
 constexpr int kTailMaxObj = 128;  // split tail rounds stage the sphere table in LDS up to this size  // per-sample setup (hashes, directions, shading) in sphere-test units
 
@@ -1020,6 +1020,10 @@ struct AoConfig {
   // ascending sphere order, so images and g-buffers are bit-identical; only the executed-tests and
   // row-cost counters change.
   static constexpr bool SORT = false;
+  // The pool's primary-ray cull masks loaded from FrameParams::cull (cull_fill_kernel wrote them
+  // with the pool start's own code) instead of computed: pool_cone_f and cone_misses_f are not
+  // compiled in.  All-sphere scenes only (planes would need a second table for pmask).
+  static constexpr bool CULLC = false;
   static constexpr int ABL = 0;        // diagnostics (A/B tools library): timing ablations, section clocks, event counts
 };
 // What the production launcher varies, as bits of AoProd's FLAGS / AoChoice::flags
@@ -1030,13 +1034,14 @@ enum : unsigned {
   AO_WIDE = 8,   // above kTailMaxObj spheres: AoConfig::PTW (else the sphere table fits the LDS rows)
   AO_CNT = 16,   // AoConfig::CNT
   AO_MF = 32,    // AoConfig::MF
+  AO_CULLC = 64, // AoConfig::CULLC
 };
 // A production configuration: split tail rounds, the batched first bounce and its pre-test always.
 template <int SPPC_, int DC_, unsigned FLAGS>
 struct AoProd : AoConfig {
   static constexpr int SPPC = SPPC_, DC = DC_;
   static constexpr bool PL = FLAGS & AO_PL, CLON = FLAGS & AO_CLON, SORT = FLAGS & AO_SORT, PTW = FLAGS & AO_WIDE,
-                        CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF;
+                        CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF, CULLC = FLAGS & AO_CULLC;
   static constexpr bool TAIL = true, B1 = true, PT = true;
 };
 
@@ -1068,11 +1073,15 @@ __host__ __device__ constexpr BatchLds batch_lds(int spp, int ntail) {
 
 // geo: the sphere table (P.sph).  The bounce-ray cluster cull of the later bounce rounds runs
 // whenever the launch has clusters (P.ncl > 0); without them the rounds test every sphere.
+// cullt: the pools' cull masks (P.cull), read by CULLC only; an argument of its own, read-only and
+// non-aliased like geo, so that its wave-uniform loads are scalar loads.
 template <class C>
-__global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P, const float4* __restrict__ geo) {
+__global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P, const float4* __restrict__ geo,
+                                                                   const unsigned long long* __restrict__ cullt) {
   constexpr int SPPC = C::SPPC, DC = C::DC, ABL = C::ABL;
   constexpr bool PL = C::PL, CLON = C::CLON, CNT = C::CNT, MF = C::MF, LAZY = C::LAZY, TAIL = C::TAIL, B1 = C::B1,
-                 PT = C::PT, PTW = C::PTW, SORT = C::SORT;
+                 PT = C::PT, PTW = C::PTW, SORT = C::SORT, CULLC = C::CULLC;
+  static_assert(!CULLC || !PL, "the cull table holds the spheres' masks only");
   __builtin_amdgcn_s_setprio(1);  // the pool's start at issue priority 1, back to 0 after the primary cull
   // CNT = false: the work counters compiled out (timed launches pass none): fewer live scalars
   unsigned long long* const cnts = CNT ? P.counters : nullptr;
@@ -1197,7 +1206,16 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
   int ncull = 0;
   const int nwords = (nobj + 63) >> 6;
   unsigned long long pmask = 0;  // PL: planes k < 64 the pool's camera rays may hit (wave-uniform)
-  {
+  if constexpr (CULLC) {
+    // the masks of pool pb as cull_fill_kernel computed them (wave-uniform address: scalar loads)
+    const unsigned long long* const ct = cullt + (size_t)pb * (unsigned)nwords;
+#pragma nounroll
+    for (int w = 0; w < nwords; ++w) {
+      const unsigned long long m = ct[w];
+      ncull += __popcll(m);
+      if (lane == 0) cmask[w] = m;
+    }
+  } else {
     const ConeF cone = pool_cone_f(P, yf == yl ? xf : 0, yf == yl ? xl : W - 1, yf, yl);
     for (int w = 0; w < nwords; ++w) {
       int i = (w << 6) + lane;
@@ -2292,6 +2310,39 @@ size_t tab_lds_bytes(const FrameParams& p) { return (size_t)5 * (p.nobj > 0 ? p.
 
 }  // namespace
 
+// The primary-ray cull of ao_batch_kernel's pool start for every pool of a launch, kept: row pb of
+// `table` holds pool pb's cmask words (pb = the pool index after the kernel's pool_rot mapping,
+// i.e. the pool of pixels [pb TP, pb TP + np), so the table does not depend on the rotation).
+// One wave per pool and the kernel's own expressions, operand for operand (this file is built with
+// -ffp-contract=off), so the masks are the ones the pool would have computed, bit for bit.
+__global__ __launch_bounds__(64) void cull_fill_kernel(FrameParams P, const float4* __restrict__ geo,
+                                                       unsigned long long* __restrict__ table) {
+  const int spp = P.spp, W = P.W, nobj = P.nobj;
+  const int TP = kPool / spp > 0 ? kPool / spp : 1;
+  const int lane = threadIdx.x;
+  const long long npix = (long long)P.trace_rows * W;
+  const unsigned pb = blockIdx.x;
+  const long long p0 = (long long)pb * TP;
+  const int np = (int)(npix - p0 < TP ? npix - p0 : TP);
+  const int yf = P.trace_row0 + (int)(p0 / W), xf = (int)(p0 % W);
+  const int yl = P.trace_row0 + (int)((p0 + np - 1) / W), xl = (int)((p0 + np - 1) % W);
+  const int nwords = (nobj + 63) >> 6;
+  const ConeF cone = pool_cone_f(P, yf == yl ? xf : 0, yf == yl ? xl : W - 1, yf, yl);
+  for (int w = 0; w < nwords; ++w) {
+    int i = (w << 6) + lane;
+    bool keep = i < nobj && !cone_misses_f(cone, geo[i], P.cx, P.cy, P.cz);
+    unsigned long long m = __ballot(keep);
+    if (lane == 0) table[(size_t)pb * (unsigned)nwords + w] = m;
+  }
+}
+
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, hipStream_t stream) {
+  const long long pools = ao_pool_count(p.trace_rows, p.W, p.spp);
+  if (pools <= 0 || p.nobj <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cull_fill_kernel, dim3((unsigned)pools), dim3(64), 0, stream, p, p.shapes + sphere_table(p.S), table);
+  return hipGetLastError();
+}
+
 constexpr int kRefDepth = 20;  // RECURSION_DEPTH, ao_compute.glsl:9
 // least spheres of a scene whose pools are sorted (RT_B1_SORT_MIN overrides: A/B builds)
 #ifndef RT_B1_SORT_MIN
@@ -2320,42 +2371,57 @@ constexpr bool operator==(const AoChoice& a, const AoChoice& b) {
 // - Above kTailMaxObj spheres the sphere table does not fit the kernel's LDS rows (AO_WIDE).
 // - Timed launches pass no counters: the counter code is compiled out.  A multi-frame launch
 //   never has counters (rt_compute_frames checks).
-constexpr AoChoice ao_select(int spp, int D, int ncl, int nobj, int nplanes, bool counters, bool multi_frame) {
+// - A launch handed a table of its pools' cull masks (FrameParams::cull) loads them (AO_CULLC);
+//   scenes with planes never are (their pmask has no table) and keep the in-kernel cull.
+constexpr AoChoice ao_select(int spp, int D, int ncl, int nobj, int nplanes, bool counters, bool multi_frame,
+                             bool cull_table) {
   const bool pl = nplanes > 0;
   const bool own = spp == 16 || spp == 4 || (spp == 64 && !pl);
   const bool clon = !pl && (spp == 16 || spp == 64) && D == kRefDepth && ncl > 0;
   return AoChoice{own ? spp : 0, clon ? kRefDepth : 0,
                   (pl ? AO_PL : 0u) | (clon ? AO_CLON : 0u) | (RT_B1_SORT && !pl && nobj >= kB1SortMinObj ? AO_SORT : 0u) |
-                      (nobj > kTailMaxObj ? AO_WIDE : 0u) | (multi_frame ? AO_MF : counters ? AO_CNT : 0u)};
+                      (nobj > kTailMaxObj ? AO_WIDE : 0u) | (multi_frame ? AO_MF : counters ? AO_CNT : 0u) |
+                      (cull_table && !pl ? AO_CULLC : 0u)};
 }
 // The dispatch's regression test (derived from the launcher this function replaced).  Arguments:
-// spp, D, ncl, nobj, nplanes, counters, multi-frame.
+// spp, D, ncl, nobj, nplanes, counters, multi-frame, cull table.
 constexpr unsigned kSortBit = RT_B1_SORT ? AO_SORT : 0u;
 // bench.py's configs, timed launch; (a) and (b) are Phong / hybrid scenes, never launched as AO
-static_assert(ao_select(1, 20, 0, 4, 0, false, false) == AoChoice{0, 0, 0}, "a");
-static_assert(ao_select(1, 20, 4, 16, 0, false, false) == AoChoice{0, 0, 0}, "b");
-static_assert(ao_select(16, 20, 8, 64, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "c");
-static_assert(ao_select(16, 20, 8, 64, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "d");
-static_assert(ao_select(64, 20, 16, 256, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "e");
-static_assert(ao_select(16, 20, 9, 65, 1, false, false) == AoChoice{16, 0, AO_PL}, "p");
-static_assert(ao_select(16, 20, 9, 65, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "q");
-static_assert(ao_select(16, 20, 0, 10, 1, false, false) == AoChoice{16, 0, AO_PL}, "s1");
-static_assert(ao_select(4, 20, 0, 10, 1, false, false) == AoChoice{4, 0, AO_PL}, "ref");
+static_assert(ao_select(1, 20, 0, 4, 0, false, false, false) == AoChoice{0, 0, 0}, "a");
+static_assert(ao_select(1, 20, 4, 16, 0, false, false, false) == AoChoice{0, 0, 0}, "b");
+static_assert(ao_select(16, 20, 8, 64, 0, false, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "c");
+static_assert(ao_select(16, 20, 8, 64, 0, false, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "d");
+static_assert(ao_select(64, 20, 16, 256, 0, false, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "e");
+static_assert(ao_select(16, 20, 9, 65, 1, false, false, false) == AoChoice{16, 0, AO_PL}, "p");
+static_assert(ao_select(16, 20, 9, 65, 0, false, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "q");
+static_assert(ao_select(16, 20, 0, 10, 1, false, false, false) == AoChoice{16, 0, AO_PL}, "s1");
+static_assert(ao_select(4, 20, 0, 10, 1, false, false, false) == AoChoice{4, 0, AO_PL}, "ref");
 // counters on; a multi-frame launch (its counters flag is ignored)
-static_assert(ao_select(16, 20, 8, 64, 0, true, false) == AoChoice{16, 20, AO_CLON | kSortBit | AO_CNT}, "counters");
-static_assert(ao_select(16, 20, 8, 64, 0, false, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
-static_assert(ao_select(16, 20, 8, 64, 0, true, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
+static_assert(ao_select(16, 20, 8, 64, 0, true, false, false) == AoChoice{16, 20, AO_CLON | kSortBit | AO_CNT}, "counters");
+static_assert(ao_select(16, 20, 8, 64, 0, false, true, false) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
+static_assert(ao_select(16, 20, 8, 64, 0, true, true, false) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF}, "multi-frame");
 // just under and at kB1SortMinObj; at and above kTailMaxObj
-static_assert(ao_select(16, 20, 6, kB1SortMinObj - 1, 0, false, false) == AoChoice{16, 20, AO_CLON}, "unsorted");
-static_assert(ao_select(16, 20, 6, kB1SortMinObj, 0, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "sorted");
-static_assert(ao_select(64, 20, 12, kTailMaxObj, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit}, "LDS table");
-static_assert(ao_select(64, 20, 12, kTailMaxObj + 1, 0, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "wide");
+static_assert(ao_select(16, 20, 6, kB1SortMinObj - 1, 0, false, false, false) == AoChoice{16, 20, AO_CLON}, "unsorted");
+static_assert(ao_select(16, 20, 6, kB1SortMinObj, 0, false, false, false) == AoChoice{16, 20, AO_CLON | kSortBit}, "sorted");
+static_assert(ao_select(64, 20, 12, kTailMaxObj, 0, false, false, false) == AoChoice{64, 20, AO_CLON | kSortBit}, "LDS table");
+static_assert(ao_select(64, 20, 12, kTailMaxObj + 1, 0, false, false, false) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE}, "wide");
 // another depth, no clusters, other spp, planes with spp 64
-static_assert(ao_select(16, 10, 8, 64, 0, false, false) == AoChoice{16, 0, kSortBit}, "depth 10");
-static_assert(ao_select(64, 20, 0, 300, 0, false, false) == AoChoice{64, 0, kSortBit | AO_WIDE}, "no clusters");
-static_assert(ao_select(4, 20, 8, 64, 0, false, false) == AoChoice{4, 0, kSortBit}, "spp 4");
-static_assert(ao_select(8, 20, 8, 64, 0, true, false) == AoChoice{0, 0, kSortBit | AO_CNT}, "spp 8");
-static_assert(ao_select(64, 20, 8, 200, 2, false, false) == AoChoice{0, 0, AO_PL | AO_WIDE}, "planes, spp 64");
+static_assert(ao_select(16, 10, 8, 64, 0, false, false, false) == AoChoice{16, 0, kSortBit}, "depth 10");
+static_assert(ao_select(64, 20, 0, 300, 0, false, false, false) == AoChoice{64, 0, kSortBit | AO_WIDE}, "no clusters");
+static_assert(ao_select(4, 20, 8, 64, 0, false, false, false) == AoChoice{4, 0, kSortBit}, "spp 4");
+static_assert(ao_select(8, 20, 8, 64, 0, true, false, false) == AoChoice{0, 0, kSortBit | AO_CNT}, "spp 8");
+static_assert(ao_select(64, 20, 8, 200, 2, false, false, false) == AoChoice{0, 0, AO_PL | AO_WIDE}, "planes, spp 64");
+// with a cull table: the same choice plus AO_CULLC, in every form but the plane scenes'
+static_assert(ao_select(16, 20, 8, 64, 0, false, false, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_CULLC}, "c, d cached");
+static_assert(ao_select(64, 20, 16, 256, 0, false, false, true) == AoChoice{64, 20, AO_CLON | kSortBit | AO_WIDE | AO_CULLC},
+              "e cached");
+static_assert(ao_select(16, 20, 8, 64, 0, true, false, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_CNT | AO_CULLC},
+              "counters cached");
+static_assert(ao_select(16, 20, 8, 64, 0, false, true, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF | AO_CULLC},
+              "multi-frame cached");
+static_assert(ao_select(8, 20, 8, 64, 0, false, false, true) == AoChoice{0, 0, kSortBit | AO_CULLC}, "spp 8 cached");
+static_assert(ao_select(16, 20, 9, 65, 1, false, false, true) == AoChoice{16, 0, AO_PL}, "p: never cached");
+static_assert(ao_select(4, 20, 0, 10, 1, false, false, true) == AoChoice{4, 0, AO_PL}, "ref: never cached");
 
 // Launch ao_batch_kernel<C> over `pools` pools: the LDS rows after the layout hold the sphere
 // table (C::PTW: one 64-sphere word of pre-test rows)
@@ -2363,11 +2429,11 @@ template <class C>
 inline void launch_ao(long long pools, hipStream_t stream, const FrameParams& q) {
   const dim3 g((unsigned)pools, C::MF ? (unsigned)q.mf_n : 1u);
   hipLaunchKernelGGL((ao_batch_kernel<C>), g, dim3(64), (size_t)batch_lds<C>(q.spp, C::PTW ? 64 : q.nobj).total, stream,
-                     q, q.sph);
+                     q, q.sph, q.cull);
 }
 // AoChoice -> AoProd: the library holds exactly the configurations ao_select can return
-template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT
-inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
+template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT | AO_CULLC
+inline void launch_ao_forms(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
   switch (flags & (AO_WIDE | AO_CNT | AO_MF)) {
     case 0: return launch_ao<AoProd<SPPC, DC, SHAPE>>(pools, stream, q);
     case AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_CNT>>(pools, stream, q);
@@ -2376,6 +2442,13 @@ inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream,
     case AO_WIDE | AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_CNT>>(pools, stream, q);
     case AO_WIDE | AO_MF: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_MF>>(pools, stream, q);
   }
+}
+template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT
+inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
+  if constexpr (!(SHAPE & AO_PL)) {
+    if (flags & AO_CULLC) return launch_ao_forms<SPPC, DC, SHAPE | AO_CULLC>(flags, pools, stream, q);
+  }
+  launch_ao_forms<SPPC, DC, SHAPE>(flags, pools, stream, q);
 }
 template <unsigned SORT>  // 0 or AO_SORT
 inline void launch_ao_choice(const AoChoice& c, long long pools, hipStream_t stream, const FrameParams& q) {
@@ -2467,7 +2540,8 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const long long npix = (long long)p.trace_rows * p.W;
     const int TP = kPool / p.spp > 0 ? kPool / p.spp : 1;
     const long long pools = (npix + TP - 1) / TP;
-    const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.counters || p.row_counters, p.mf_n > 0);
+    const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.counters || p.row_counters, p.mf_n > 0,
+                                 q.cull != nullptr);
     // (kSortBit: a build with RT_B1_SORT=0 never selects the sort and compiles no SORT instantiation)
     if (c.flags & AO_SORT) launch_ao_choice<kSortBit>(c, pools, stream, q);
     else launch_ao_choice<0>(c, pools, stream, q);

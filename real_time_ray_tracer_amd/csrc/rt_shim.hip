@@ -82,6 +82,46 @@ struct TileSched {
 };
 constexpr int kSchedPeriod = 16;
 
+// Cull cache.  The AO kernel's pool start culls the sphere table against the cone of the pool's
+// primary rays; its inputs are the camera, the frame and strip geometry, spp, nobj and the sphere
+// rows (cull_key), none of which the render loop's per-frame update touches (it replaces
+// rand_buffer and mode.y).  While the key holds, the pools' masks are kept in a device table
+// (rt::launch_cull_fill) and the AO launches load them (FrameParams::cull):
+//  - a launch whose key differs from the previous launch's runs the in-kernel cull and marks the
+//    table invalid; so does the first launch that repeats a key (a camera that rests for one
+//    frame pays nothing);
+//  - the second launch in a row that repeats the key enqueues the fill on its own stream, before
+//    itself, when the table is invalid; it and its successors load the masks.
+// Nothing waits on the host.  Pipelined AO passes alternate between streams: a stream's first
+// cached launch after a fill waits for the fill's event, and a refill waits for the events of
+// the last cached launches on every stream (recorded when the table was marked invalid).
+// Tables above kCullCacheMaxBytes are never built: those contexts, scenes with planes, and contexts
+// whose allocation failed keep the in-kernel cull.  The cap admits config (e)'s 265 MB (7680x4320,
+// 64 spp, 256 spheres: 8.3 M pools of 4 words, 1.5% of what that context's g-buffer ring holds),
+// whose launches gain 2% from it (DESIGN.md §5 "Round 9").
+#ifndef RT_CULL_CACHE_MAX_MB
+#define RT_CULL_CACHE_MAX_MB 512  // (A/B builds override it)
+#endif
+constexpr size_t kCullCacheMaxBytes = (size_t)RT_CULL_CACHE_MAX_MB << 20;
+constexpr int kCullRepeats = 2;  // launches in a row that must repeat a key before the table is filled
+struct CullCache {
+  bool on = true;                    // rt_set_cull_cache
+  bool nomem = false;                // the allocation failed once: never cached
+  unsigned long long* d_table = nullptr;
+  size_t bytes = 0;                  // of d_table: pools x ceil(num_shapes / 64) words
+  std::vector<unsigned char> key;    // the previous eligible launch's key
+  std::vector<unsigned char> next;   // scratch: the key of the launch being made
+  bool have_key = false;
+  int repeats = 0;                   // launches in a row that repeated `key`
+  bool valid = false;                // d_table holds `key`'s masks
+  hipEvent_t ev_fill = nullptr;
+  hipStream_t seen[kAoStreams] = {};     // streams ordered after the fill
+  hipStream_t readers[kAoStreams] = {};  // streams with cached launches since the fill
+  hipEvent_t ev_read[kAoStreams] = {};   // the last cached launches, one per reader stream
+  int n_read = 0;                    // ev_read[0 .. n_read) are recorded and not yet waited for
+  long long fills = 0, cached = 0;   // rt_cull_cache_stats
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -125,6 +165,7 @@ struct rt_ctx {
   int batch_last = -1;         // the d_batch slot d_shapes points into after rt_compute_frames (else -1)
   TileSched sched[kSchedKinds];  // longest-first schedules (set up by the first launch of each kind)
   bool sched_on = true;          // rt_set_tile_schedule
+  CullCache cull;                // the AO pools' primary-ray cull masks while camera and scene hold
   float4* d_mf_rb = nullptr;   // rt_compute_frames, mode 2: the rand_buffers of a multi-frame launch
   std::vector<float4> batch_host;
   std::vector<float> batch_hdr;  // the batch's host headers (camera, light: launch parameters)
@@ -243,6 +284,10 @@ void free_sched(TileSched& h) {
 
 void free_all(rt_ctx* c) {
   for (auto& h : c->sched) free_sched(h);
+  if (c->cull.d_table) (void)hipFree(c->cull.d_table);
+  if (c->cull.ev_fill) (void)hipEventDestroy(c->cull.ev_fill);
+  for (auto e : c->cull.ev_read)
+    if (e) (void)hipEventDestroy(e);
   for (auto& s : c->stage) {
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.host) (void)hipHostFree(s.host);
@@ -358,7 +403,129 @@ void fill_params(const rt_ctx* c, int frame, rt::FrameParams& p) {
   p.row_counters = c->row_counting ? c->d_row_counters : nullptr;
 }
 
-int launch(rt_ctx* c, int program, const rt::FrameParams& p, hipStream_t st) {
+// The cull cache's key of a context configuration (rows resolved: row_begin < row_end) and header
+// h: the exact bytes of every input of the AO pool start's primary-ray cull (see CullCache) and the
+// launch's pool count.  Written to `out` when it fits in cap bytes; returns the key's size, 0 for a
+// header whose int(mode.z) is out of range.
+size_t cull_key(const rt_config& cfg, const float* h, unsigned char* out, size_t cap) {
+  const float mz = h[RT_HDR_MODE * 4 + 2];
+  if (!(mz >= 0.0f && mz < (float)(cfg.num_shapes + 1))) return 0;
+  const int nobj = (int)mz;
+  const int band0 = std::max(0, cfg.row_begin - 1);
+  const int band_rows = std::min(cfg.height, cfg.row_end + 1) - band0;  // the AO launches' rows (strip + halo)
+  const long long pools = rt::ao_pool_count(band_rows, cfg.width, cfg.spp);
+  // (pool_rot is a function of W and spp, rt_kernels_impl.h launch_params)
+  const int ints[6] = {cfg.width, cfg.height, band0, band_rows, cfg.spp, nobj};
+  const float dims[2] = {(float)cfg.width, (float)cfg.height};
+  size_t n = 0;
+  auto put = [&](const void* src, size_t bytes) {
+    if (out && n + bytes <= cap) std::memcpy(out + n, src, bytes);
+    n += bytes;
+  };
+  put(ints, sizeof(ints));
+  put(&pools, sizeof(pools));
+  put(dims, sizeof(dims));
+  for (int v : {RT_HDR_HORIZONTAL, RT_HDR_VERTICAL, RT_HDR_LLC_MINUS_CAMPOS, RT_HDR_CAMERA_LOCATION})
+    put(h + 4 * v, 3 * sizeof(float));
+  const float* sh = h + rt_off_shapes() / 4;
+  for (int i = 0; i < nobj; ++i) {  // the sphere table's row i: the geometry, or NaN by the shape id
+    put(sh + (size_t)i * 20, 4 * sizeof(float));
+    put(sh + (size_t)i * 20 + 19, sizeof(float));
+  }
+  return n;
+}
+
+// the table is no longer the current key's: the cached launches enqueued so far are its last readers
+int cull_invalidate(rt_ctx* c) {
+  CullCache& k = c->cull;
+  if (!k.valid) return RT_OK;
+  k.valid = false;
+  for (auto& s : k.readers) {
+    if (!s) continue;
+    if (!k.ev_read[k.n_read]) RT_HIP(c, hipEventCreateWithFlags(&k.ev_read[k.n_read], hipEventDisableTiming));
+    RT_HIP(c, hipEventRecord(k.ev_read[k.n_read], s));
+    ++k.n_read;
+    s = nullptr;
+  }
+  return RT_OK;
+}
+
+// every stream has been drained (sync_all): nothing in flight reads or writes the table
+void cull_streams_idle(rt_ctx* c) {
+  CullCache& k = c->cull;
+  k.n_read = 0;
+  for (auto& s : k.readers) s = nullptr;
+  for (auto& s : k.seen) s = nullptr;
+}
+
+bool cull_note(hipStream_t* set, hipStream_t st) {  // adds st; false if it was there
+  for (int s = 0; s < kAoStreams; ++s) {
+    if (set[s] == st) return false;
+    if (!set[s]) {
+      set[s] = st;
+      return true;
+    }
+  }
+  set[0] = st;  // (never: a context launches AO passes on at most kAoStreams streams between two drains)
+  return true;
+}
+
+// Before an AO launch of p on st: compare its key with the previous launch's and hand it the
+// table (p.cull) when the key has held, after filling the table if it is invalid (see CullCache).
+int cull_before(rt_ctx* c, rt::FrameParams& p, hipStream_t st) {
+  CullCache& k = c->cull;
+  p.cull = nullptr;
+  const int nwmax = (c->cfg.num_shapes + 63) / 64;
+  const size_t need = (size_t)rt::ao_pool_count(p.trace_rows, p.W, p.spp) * nwmax * sizeof(unsigned long long);
+  const bool whole_band = p.trace_row0 == c->band0 && p.trace_rows == c->band_rows;  // (every AO launch's rows)
+  if (!k.on || k.nomem || p.nplanes > 0 || p.nobj <= 0 || !whole_band || need == 0 || need > kCullCacheMaxBytes) {
+    k.have_key = false;
+    return cull_invalidate(c);
+  }
+  std::vector<unsigned char>& key = k.next;
+  key.resize(cull_key(c->cfg, c->header.data(), nullptr, 0));
+  if (key.empty() || cull_key(c->cfg, c->header.data(), key.data(), key.size()) != key.size()) {
+    k.have_key = false;
+    return cull_invalidate(c);
+  }
+  if (!k.have_key || key != k.key) {
+    k.key.swap(key);
+    k.have_key = true;
+    k.repeats = 0;
+    return cull_invalidate(c);
+  }
+  if (++k.repeats < kCullRepeats) return RT_OK;
+  k.repeats = kCullRepeats;
+  if (!k.valid) {
+    if (!k.d_table) {  // lazily; a failed allocation leaves the context uncached
+      const hipError_t e = hipMalloc(&k.d_table, need);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        k.d_table = nullptr;
+        k.nomem = true;
+        return RT_OK;
+      }
+      k.bytes = need;
+    }
+    if (!k.ev_fill) RT_HIP(c, hipEventCreateWithFlags(&k.ev_fill, hipEventDisableTiming));
+    for (int s = 0; s < k.n_read; ++s) RT_HIP(c, hipStreamWaitEvent(st, k.ev_read[s], 0));
+    k.n_read = 0;
+    const hipError_t e = rt::launch_cull_fill(p, k.d_table, st);
+    if (e != hipSuccess) return hip_fail(c, e);
+    RT_HIP(c, hipEventRecord(k.ev_fill, st));
+    for (auto& s : k.seen) s = nullptr;
+    k.seen[0] = st;
+    k.valid = true;
+    k.fills += 1;
+  }
+  if (cull_note(k.seen, st)) RT_HIP(c, hipStreamWaitEvent(st, k.ev_fill, 0));
+  cull_note(k.readers, st);
+  p.cull = k.d_table;
+  k.cached += 1;
+  return RT_OK;
+}
+
+int launch_timed(rt_ctx* c, int program, const rt::FrameParams& p, hipStream_t st) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (c->timing) {
     e0 = get_event(c);
@@ -374,6 +541,14 @@ int launch(rt_ctx* c, int program, const rt::FrameParams& p, hipStream_t st) {
     c->pending[program].push_back(rt_ctx::Timed{e0, e1, p.mf_n > 0 ? p.mf_n : 1});
   }
   return RT_OK;
+}
+// A launch of `program`; the AO passes with their cull table when the cache holds one (the fill, if
+// any, goes before the timed bracket)
+int launch(rt_ctx* c, int program, const rt::FrameParams& p, hipStream_t st) {
+  if (program != RT_PROG_AO_COMPUTE && program != RT_PROG_AOP_COMPUTE) return launch_timed(c, program, p, st);
+  rt::FrameParams q = p;
+  int rc = cull_before(c, q, st);
+  return rc == RT_OK ? launch_timed(c, program, q, st) : rc;
 }
 int launch(rt_ctx* c, int program, const rt::FrameParams& p) { return launch(c, program, p, c->stream); }
 
@@ -813,6 +988,7 @@ int rt_set_stream(rt_ctx* c, void* s) {
   for (auto& r : c->post_recorded) r = false;
   c->pipe_n = 0;
   c->img_stream = nullptr;  // everything is finished (sync_all above)
+  cull_streams_idle(c);
   for (auto& h : c->sched)  // no launch reads an order table any more: forget the old streams
     for (auto& u : h.used_on)
       for (auto& st : u) st = nullptr;
@@ -843,6 +1019,7 @@ int rt_enable_pipelining(rt_ctx* c, int on, void* output_stream) {
   for (auto& r : c->post_recorded) r = false;
   c->pipe_n = 0;
   c->img_stream = nullptr;
+  cull_streams_idle(c);
   c->pipelined = on != 0;
   if (!c->pipelined) {
     c->out_stream = c->stream;
@@ -1299,6 +1476,32 @@ int rt_tile_schedule_orders(rt_ctx* c) {
   int n = 0;
   for (auto& h : c->sched) n += h.orders_taken;
   return n;
+}
+
+int rt_set_cull_cache(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  RT_HIP(c, hipSetDevice(c->device));
+  c->cull.on = on != 0;
+  c->cull.have_key = false;  // on again: the key has to hold anew
+  return cull_invalidate(c);
+}
+
+int rt_cull_cache_stats(rt_ctx* c, long long* fills, long long* cached_launches, size_t* table_bytes) {
+  if (!c) return RT_E_INVAL;
+  if (fills) *fills = c->cull.fills;
+  if (cached_launches) *cached_launches = c->cull.cached;
+  if (table_bytes) *table_bytes = c->cull.bytes;
+  return RT_OK;
+}
+
+size_t rt_cull_key(const rt_config* cfg, const void* header, size_t header_bytes, void* key, size_t key_cap) {
+  if (!cfg || !header || cfg->width <= 0 || cfg->height <= 0 || cfg->spp <= 0 || cfg->num_shapes < 0 ||
+      header_bytes != rt_header_bytes(cfg->num_shapes, cfg->spp))
+    return 0;
+  rt_config x = *cfg;
+  if (x.row_begin == 0 && x.row_end == 0) x.row_end = x.height;  // as rt_create
+  if (x.row_begin < 0 || x.row_end > x.height || x.row_begin >= x.row_end) return 0;
+  return cull_key(x, (const float*)header, (unsigned char*)key, key_cap);
 }
 
 int rt_set_frame_batch(rt_ctx* c, int max_frames) {

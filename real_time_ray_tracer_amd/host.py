@@ -265,6 +265,17 @@ class Renderer:
         """Orders taken up so far (rt_tile_schedule_orders)."""
         return self._c(self._lib.rt_tile_schedule_orders(self.ctx), "rt_tile_schedule_orders")
 
+    def set_cull_cache(self, on: bool):
+        """The AO pools' primary-ray cull masks kept while camera and scene hold (rt_set_cull_cache;
+        on by default).  Off: every launch culls in the kernel; results are bit-identical."""
+        self._c(self._lib.rt_set_cull_cache(self.ctx, int(bool(on))), "rt_set_cull_cache")
+
+    def cull_cache_stats(self) -> dict:
+        """{"fills", "cached_launches", "table_bytes"} since the context was created (rt_cull_cache_stats)."""
+        f, n, b = C.c_longlong(), C.c_longlong(), C.c_size_t()
+        self._c(self._lib.rt_cull_cache_stats(self.ctx, C.byref(f), C.byref(n), C.byref(b)), "rt_cull_cache_stats")
+        return {"fills": f.value, "cached_launches": n.value, "table_bytes": b.value}
+
     def download(self, pixels=True, normals=True, depth=True, image=True) -> GBuffer:
         shp = (self.F, self.W, self.R, 4)
         p = np.empty(shp, np.float32) if pixels else None

@@ -1,0 +1,257 @@
+"""The AO cull cache (rt_set_cull_cache, rt_shim CullCache): while camera and scene hold, the pools
+of an AO launch load their primary-ray cull masks from a table instead of computing them.  The
+reference in every case is the same library with the cache off on a second context fed the same
+headers; images, pixels, normals and depth must be equal bit for bit, and with the counters on the
+work counters and the row counters too.  Shapes: the smallest at which the table's index or the
+key can go wrong (pools that straddle row ends, partial last pools and rotation groups, a strip
+with trace_row0 != 0, one to three mask words, every constant-spp instantiation and spp 8).
+
+A table is filled by the second launch in a row that repeats the previous launch's key, so a still
+sequence runs frames 0 and 1 uncached and every later one cached."""
+import numpy as np
+import pytest
+
+from conftest import assert_bitwise
+from real_time_ray_tracer_amd import Header, Renderer, aspect_for
+from test_gpu_parity import make_header
+
+pytestmark = pytest.mark.gpu
+
+CAM = 4  # RT_HDR_CAMERA_LOCATION (include/rt/layout.h)
+
+
+def render(h0, W, H, frames, cache, mutate=None, mode=1, rows=None, counters=False, toggle=None, after=None):
+    """`frames` frames of `mode` from header h0: per frame mutate(k, h), then the render loop's own
+    update (rand_buffer, mode.y), upload, dispatch.  Returns (g-buffer, stats, counters)."""
+    r = Renderer(W, H, h0.S, h0.AA, rows=rows)
+    if not cache:
+        r.set_cull_cache(False)
+    if counters:
+        r.enable_counters(True, rows=True)
+    h = h0.copy()
+    f = 0
+    for k in range(frames):
+        if mutate:
+            mutate(k, h)
+        if toggle and cache:
+            toggle(k, r)
+        h.fill_rand_buffer(7000 + k)
+        h.set_mode(f, h.num_objects)
+        r.upload_header(h)
+        f = r.dispatch(mode, f)
+        if after:
+            after(k, r)
+    g = r.download()
+    stats = r.cull_cache_stats()
+    cnt = (r.read_counters(), r.read_row_counters()) if counters else None
+    r.close()
+    return g, stats, cnt
+
+
+def same(a, b, what=""):
+    (ga, _, ca), (gb, _, cb) = a, b
+    for name in ("image", "pixels", "normals", "depth"):
+        assert_bitwise(getattr(ga, name), getattr(gb, name), f"{what} {name}")
+    if ca is not None:
+        assert ca[0] == cb[0], f"{what} work counters: {ca[0]} vs {cb[0]}"
+        assert np.array_equal(ca[1], cb[1]), f"{what} row counters"
+
+
+def both(h, W, H, frames, **kw):
+    on = render(h, W, H, frames, True, **kw)
+    off = render(h, W, H, frames, False, **kw)
+    same(on, off, f"{W}x{H}")
+    assert off[1]["cached_launches"] == 0 and off[1]["fills"] == 0
+    return on, off
+
+
+@pytest.mark.parametrize("counters", [False, True])
+@pytest.mark.parametrize("W,H", [(40, 12), (64, 8), (72, 8)])
+def test_row_straddling_and_partial_pools(W, H, counters):
+    """spp 16, pools of 16 pixels.  40 x 12: pools straddle row ends, the last pool is partial
+    (480 pixels = 30 pools).  64 x 8: 32 pools, four whole rotation groups of 8.  72 x 8: 36 pools,
+    a trailing partial rotation group."""
+    on, _ = both(make_header("syn64", W, H, 16), W, H, 5, counters=counters)
+    assert on[1] == {"fills": 1, "cached_launches": 3, "table_bytes": (W * H + 15) // 16 * 8}
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_strip_context(mode):
+    """rows (5, 11) of a 64 x 16 frame: trace_row0 = 4 (the halo row), 8 traced rows."""
+    on, _ = both(make_header("syn64", 64, 16, 16), 64, 16, 5, rows=(5, 11), mode=mode, counters=True)
+    assert on[1]["fills"] == 1 and on[1]["cached_launches"] == 3
+
+
+@pytest.mark.parametrize("spp", [4, 16, 64])
+@pytest.mark.parametrize("n", [48, 64, 65, 128, 130])
+def test_sphere_counts(n, spp):
+    """One, two and three mask words; 128 / 130: the LDS-table and the word-by-word (AO_WIDE)
+    instantiations; spp 4, 16, 64: the constant-spp ones.  With counters (AO_CNT), 40 x 6: partial
+    last pools at spp 4 and 16."""
+    on, _ = both(make_header(f"syn{n}", 40, 6, spp), 40, 6, 4, counters=True)
+    assert on[1]["fills"] == 1 and on[1]["cached_launches"] == 2
+    assert on[1]["table_bytes"] == (40 * 6 + 256 // spp - 1) // (256 // spp) * ((n + 63) // 64) * 8
+
+
+@pytest.mark.parametrize("counters", [False, True])
+def test_spp_8(counters):
+    """spp 8 has no instantiation of its own: P.spp at run time (SPPC = 0)."""
+    on, _ = both(make_header("syn64", 40, 6, 8), 40, 6, 4, counters=counters)
+    assert on[1]["cached_launches"] == 2
+
+
+def test_all_sky():
+    """Every sphere far outside the view: every mask is zero, every pool takes the sky exit."""
+    W, H = 40, 6
+    h = Header.synthetic(48, 16, 1234, aspect_for(W, H))
+    for i in range(48):
+        h.pack_sphere(i, (1000.0 + 3.0 * i, 0.0, 0.0), 1.0, (0.5, 0.5, 0.5))
+    on, _ = both(h, W, H, 4, counters=True)
+    assert on[1]["cached_launches"] == 2 and not on[0].normals.any()
+
+
+def test_camera_inside_a_sphere():
+    """cone_misses_f keeps a sphere the camera is inside of or near (its d2 > reff2 ... branch)."""
+    W, H = 40, 6
+    h = make_header("syn64", W, H, 16)
+    h.pack_sphere(3, tuple(h.vec4(CAM)[:3]), 5.0, (0.6, 0.7, 0.8))
+    on, _ = both(h, W, H, 4, counters=True)
+    assert on[1]["cached_launches"] == 2 and on[0].normals.any()
+
+
+def test_engagement():
+    """Six frames, still camera: one fill; frames 0 and 1 run uncached, frames 2..5 cached."""
+    seen = []
+    on, _ = both(make_header("syn64", 40, 12, 16), 40, 12, 6,
+                 after=lambda k, r: seen.append(r.cull_cache_stats()["cached_launches"]))
+    assert on[1]["fills"] == 1 and on[1]["cached_launches"] == 4
+    assert seen[:6] == [0, 0, 1, 2, 3, 4]
+
+
+def _cam_ulp(h):
+    h.vec4(CAM)[0] = np.nextafter(h.vec4(CAM)[0], np.float32(np.inf))
+
+
+def _cam_basis(h):
+    h.camera_basis((0.0, 0.0, 14.0), (0.0, 1.0, 0.0), (0.05, 0.0, 1.0), aspect_for(40, 12))
+
+
+def _radius(h):
+    h.shapes[5, 0, 3] *= np.float32(1.25)
+
+
+def _moved(h):
+    h.shapes[5, 0, 0] += np.float32(0.5)
+
+
+def _fewer(h):
+    h.set_mode(0, h.num_objects - 1)
+
+
+@pytest.mark.parametrize("change,refills", [(_cam_ulp, True), (_cam_basis, True), (_radius, True), (_moved, True),
+                                            (_fewer, True), (None, False)],
+                         ids=["camera-ulp", "camera-basis", "radius", "moved", "nobj", "same-header"])
+def test_invalidation(change, refills):
+    """Three still frames, one change, three still frames.  A change of any key input: the frame
+    with the change and the next run uncached, the one after refills.  The same header uploaded
+    again: no refill."""
+    def mutate(k, h):
+        if k == 3 and change:
+            change(h)
+    on, _ = both(make_header("syn64", 40, 12, 16), 40, 12, 7, mutate=mutate, counters=True)
+    if refills:
+        assert on[1]["fills"] == 2 and on[1]["cached_launches"] == 1 + 2
+    else:
+        assert on[1]["fills"] == 1 and on[1]["cached_launches"] == 5
+
+
+def test_moving_camera():
+    """The camera changes every frame: no table is ever built."""
+    def mutate(k, h):
+        h.vec4(CAM)[0] += np.float32(0.01)
+    on, _ = both(make_header("syn64", 40, 12, 16), 40, 12, 8, mutate=mutate)
+    assert on[1]["cached_launches"] == 0 and on[1]["fills"] == 0 and on[1]["table_bytes"] == 0
+
+
+def test_pipelined_with_torch_output_stream():
+    """Pipelined mode 1, 21 frames (the 8-slot ring wraps), output on a torch stream; the camera
+    moves at frames 5 and 6 (two in a row) and at frame 13.  Against the sequential, uncached order."""
+    import torch
+
+    W, H, spp = 96, 64, 4
+    h0 = Header.synthetic(64, spp, 99, aspect_for(W, H))  # 1/16 emissive spheres: stale path
+    dev = torch.device("cuda", 0)
+    main, out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+
+    def frames(r, h):
+        f = 0
+        for k in range(21):
+            if k in (5, 6, 13):
+                h.vec4(CAM)[0] += np.float32(0.25)
+            h.fill_rand_buffer(7000 + k)
+            h.set_mode(f, h.num_objects)
+            r.upload_header(h)
+            f = r.dispatch(1, f)
+
+    a = Renderer(W, H, h0.S, spp)
+    a.set_cull_cache(False)
+    frames(a, h0.copy())
+    b = Renderer(W, H, h0.S, spp)
+    b.set_stream(main)
+    b.enable_pipelining(True, out)
+    img = torch.zeros((H, W, 4), dtype=torch.float32, device=dev)
+    b.bind_image(img.data_ptr())
+    frames(b, h0.copy())
+    with torch.cuda.stream(out):
+        got = img.cpu().numpy()
+    assert_bitwise(got, a.image(), "image on the output stream")
+    ga, gb = a.download(True, True, True, False), b.download(True, True, True, False)
+    for name in ("pixels", "normals", "depth"):
+        assert_bitwise(getattr(gb, name), getattr(ga, name), name)
+    s = b.cull_cache_stats()
+    # the keys hold over frames 0..4, 6..12 and 13..20: each run fills once, at its third frame
+    assert s["fills"] == 3 and s["cached_launches"] == 3 + 5 + 6, s
+    a.close()
+    b.close()
+
+
+def test_multi_frame_launches_across_an_invalidation():
+    """Mode 2, rt_compute_frames with 8 frames per launch: three launches, the camera moves, three
+    more.  Every frame of a cached launch reads the same table."""
+    W, H = 40, 12
+    h0 = make_header("syn64", W, H, 16)
+    out = []
+    for cache in (True, False):
+        r = Renderer(W, H, h0.S, h0.AA)
+        r.set_frame_batch(8)
+        if not cache:
+            r.set_cull_cache(False)
+        h = h0.copy()
+        f = 0
+        for k in range(6):
+            if k == 3:
+                h.vec4(CAM)[0] += np.float32(0.25)
+            f = r.compute_frames(h, 2, f, 8, rand_seed=7000 + 8 * k)
+        out.append((r.download(), r.cull_cache_stats(), None))
+        r.close()
+    same(out[0], out[1], "multi-frame")
+    assert out[0][1]["fills"] == 2 and out[0][1]["cached_launches"] == 2
+
+
+@pytest.mark.parametrize("scene", ["syn56p", "s1"])
+def test_plane_scene_is_never_cached(scene):
+    W, H = 40, 12
+    on, _ = both(make_header(scene, W, H, 16), W, H, 5, counters=True)
+    assert on[1] == {"fills": 0, "cached_launches": 0, "table_bytes": 0}
+
+
+def test_toggled_off_and_on():
+    """Off at frame 4 (frames 2, 3 ran cached), on again at frame 7: the key has to hold anew, so
+    frames 7 and 8 run uncached and frame 9 refills."""
+    def toggle(k, r):
+        if k == 4:
+            r.set_cull_cache(False)
+        if k == 7:
+            r.set_cull_cache(True)
+    on, _ = both(make_header("syn64", 40, 12, 16), 40, 12, 12, toggle=toggle, counters=True)
+    assert on[1]["fills"] == 2 and on[1]["cached_launches"] == 2 + 3

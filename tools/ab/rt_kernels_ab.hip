@@ -197,7 +197,7 @@ static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t strea
   // every variant's LDS rows after the layout: ntail float4 (the sphere table where the variant stages it)
   auto go = [&](auto cfg, int ntail) {
     using C = decltype(cfg);
-    hipLaunchKernelGGL((ao_batch_kernel<C>), g, b, (size_t)batch_lds<C>(p.spp, ntail).total, stream, q, q.sph);
+    hipLaunchKernelGGL((ao_batch_kernel<C>), g, b, (size_t)batch_lds<C>(p.spp, ntail).total, stream, q, q.sph, q.cull);
   };
   if (variant == 93 && p.nplanes > 0) {  // section clocks of the production plane kernel
     if (tl && p.spp == 16) go(Abl<PlaneCounted16, 3>{}, p.nobj);
