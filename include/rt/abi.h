@@ -167,6 +167,16 @@ int rt_set_cull_cache(rt_ctx* ctx, int on);
 /* Table fills and AO launches that loaded their masks since rt_create, and the table's bytes
  * (0 until the first fill).  Any pointer may be NULL. */
 int rt_cull_cache_stats(rt_ctx* ctx, long long* fills, long long* cached_launches, size_t* table_bytes);
+/* The fill also keeps, per pool, a frame on the surface normal at the hit of the pool's unjittered
+ * centre ray (32 bytes per pool, allocated with the masks); the sorted AO kernels then deal the
+ * pool's samples to its batches by their sector around that normal.  It changes the order of work
+ * only, never a result.  When masks and frames together would exceed the cap or cannot be
+ * allocated, the context keeps the masks alone.  Returns the frames' bytes (0 until the first
+ * fill, and for a context that keeps masks only). */
+size_t rt_cull_cache_frame_bytes(rt_ctx* ctx);
+/* Test hook: this context's cap on the cull cache's bytes, in place of the build's 512 MiB
+ * (0 restores it).  Before the first fill only. */
+int rt_debug_cull_cache_cap(rt_ctx* ctx, size_t bytes);
 /* The cull cache's key of `header` (rt_header_bytes(num_shapes, spp) bytes) for a context created
  * with `cfg`: written to `key` when it fits in key_cap bytes (key may be NULL).  Returns the key's
  * size in bytes, 0 for an invalid configuration or header.  Two launches share a table iff their

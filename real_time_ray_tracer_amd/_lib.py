@@ -63,6 +63,8 @@ SIGNATURES = {
     "rt_tile_schedule_orders": (C.c_int, [_ctx]),
     "rt_set_cull_cache": (C.c_int, [_ctx, C.c_int]),
     "rt_cull_cache_stats": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]),
+    "rt_cull_cache_frame_bytes": (C.c_size_t, [_ctx]),
+    "rt_debug_cull_cache_cap": (C.c_int, [_ctx, C.c_size_t]),
     "rt_cull_key": (C.c_size_t, [C.POINTER(rt_config), _vp, C.c_size_t, _vp, C.c_size_t]),
     "rt_download": (C.c_int, [_ctx, _fp, _fp, _fp, _fp]),
     "rt_download_rect": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),

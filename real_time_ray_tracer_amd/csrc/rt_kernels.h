@@ -46,6 +46,8 @@ struct FrameParams {
   float lx, ly, lz;          // llc_minus_campos
   float cx, cy, cz;          // camera_location
   float Lx, Ly, Lz;          // light_pos
+  int cull_frames;           // AO: `cull` is preceded by the pools' sort frames (below); in the padding in front of bg,
+                             // so no other member and no kernel argument moves
   float4 bg;                 // background
   const float4* shapes;      // compact table [4][S]: geo, geo2, col, aux (rt_device.h)
   // derived from `shapes` by launch_program (sphere_table / plane_table below):
@@ -91,9 +93,18 @@ struct FrameParams {
   unsigned* tile_cost;
   // AO, all-sphere scenes: the pools' primary-ray cull masks, [pools][(nobj + 63) / 64] u64 as
   // launch_cull_fill wrote them for this camera, scene and strip; non-null selects the kernels
-  // that load their pool's masks instead of computing them (nullptr: the in-kernel cull)
+  // that load their pool's masks instead of computing them (nullptr: the in-kernel cull).
+  // cull_frames != 0: the same allocation holds, in front of the masks, pool pb's sort frame at
+  // (const float4*)cull - 2 (pb + 1): (e1, 0), (e2, 0), two unit vectors orthogonal to the surface
+  // normal at the hit of the pool's unjittered centre ray (launch_cull_fill); the sorted kernels
+  // then deal the pool's samples by the sector of their bounce hemisphere point around that normal
   const unsigned long long* cull;
 };
+static_assert(offsetof(FrameParams, bg) == 160 && offsetof(FrameParams, cull_frames) == 156,
+              "cull_frames fills the padding in front of bg");
+
+// bytes of the sort frames in front of a cull table of `pools` pools (two float4 per pool)
+constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2 * sizeof(float4); }
 
 // AO pools: kAoPool samples each, i.e. max(1, kAoPool / spp) consecutive pixels of the launch's rows
 constexpr int kAoPool = 256;
@@ -139,7 +150,12 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream)
 // primary-ray cull masks an AO launch of p computes per pool: the same device functions on the same
 // operands, so a launch that reads them through FrameParams::cull renders what it would have.
 // They depend on p's camera, frame and strip geometry, spp, nobj and sphere rows only.
-hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, hipStream_t stream);
+// frames: the ao_cull_frame_bytes(pools) bytes in front of `table` are written too (FrameParams::
+// cull_frames): per pool the unjittered ray through its middle pixel is traced against the pool's
+// own surviving spheres, and the frame is built on the hit's normal (a miss: on the reversed ray).
+// Same inputs as the masks, the same values from run to run; nothing computed from a frame
+// reaches a result, it only orders a pool's samples.
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream);
 
 // g-buffer layout conversion between the reference's [F][W][R] vec4 (x-major, y fastest:
 // src/main.cpp:49-85 over a context's R rows) and the device slots of one array kind (0 pixels:

@@ -1024,6 +1024,10 @@ struct AoConfig {
   // with the pool start's own code) instead of computed: pool_cone_f and cone_misses_f are not
   // compiled in.  All-sphere scenes only (planes would need a second table for pmask).
   static constexpr bool CULLC = false;
+  // With SORT and CULLC: the sort keyed on the pool's cached sort frame (FrameParams::cull_frames,
+  // cull_fill_kernel) when the launch has one: hemi's 45-degree sector around the surface normal
+  // at the pool's centre ray instead of hemi's world octant.  The same bit-identical results.
+  static constexpr bool NSORT = false;
   static constexpr int ABL = 0;        // diagnostics (A/B tools library): timing ablations, section clocks, event counts
 };
 // What the production launcher varies, as bits of AoProd's FLAGS / AoChoice::flags
@@ -1036,12 +1040,18 @@ enum : unsigned {
   AO_MF = 32,    // AoConfig::MF
   AO_CULLC = 64, // AoConfig::CULLC
 };
+// The forms that key the sort on the pool's frame: sorted and cached, not the counter forms (their
+// work counters stay those of the uncached launch, whose key is the octant), never with planes.
+constexpr bool ao_sorts_by_frame(unsigned flags) {
+  return (flags & (AO_SORT | AO_CULLC | AO_CNT | AO_PL)) == (AO_SORT | AO_CULLC);
+}
 // A production configuration: split tail rounds, the batched first bounce and its pre-test always.
 template <int SPPC_, int DC_, unsigned FLAGS>
 struct AoProd : AoConfig {
   static constexpr int SPPC = SPPC_, DC = DC_;
   static constexpr bool PL = FLAGS & AO_PL, CLON = FLAGS & AO_CLON, SORT = FLAGS & AO_SORT, PTW = FLAGS & AO_WIDE,
-                        CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF, CULLC = FLAGS & AO_CULLC;
+                        CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF, CULLC = FLAGS & AO_CULLC,
+                        NSORT = ao_sorts_by_frame(FLAGS);
   static constexpr bool TAIL = true, B1 = true, PT = true;
 };
 
@@ -1071,6 +1081,29 @@ __host__ __device__ constexpr BatchLds batch_lds(int spp, int ntail) {
   return batch_lds_of(spp, ntail, !C::PTW, C::SORT);
 }
 
+// The SORT pre-pass keyed on a pool's sort frame (e1, e2): a sample's three bits are a < 0 (bit 0),
+// b < 0 (bit 1) and |a| < |b| (bit 2) of a = dot(hemi, e1), b = dot(hemi, e2), i.e. the 45-degree
+// sector of hemi's azimuth around the normal.  sector_bits: the bits of a point; sector_code(s):
+// the bits of sector s, [45 s, 45 s + 45) degrees from e1 towards e2.  The sort's bin s holds
+// sector s, so neighbouring bins (and the last and the first) are neighbouring sectors.
+constexpr int sector_bits(float a, float b) {
+  return (a < 0.0f ? 1 : 0) | (b < 0.0f ? 2 : 0) | ((a < 0.0f ? -a : a) < (b < 0.0f ? -b : b) ? 4 : 0);
+}
+__host__ __device__ constexpr int sector_code(int s) { return (int)(0x26731540u >> (4 * s)) & 7; }
+constexpr bool sector_code_ok() {
+  // a point inside each sector, counter-clockwise from e1
+  constexpr float pa[8] = {2, 1, -1, -2, -2, -1, 1, 2}, pb[8] = {1, 2, 2, 1, -1, -2, -2, -1};
+  unsigned seen = 0;
+  for (int s = 0; s < 8; ++s) {
+    if (sector_code(s) != sector_bits(pa[s], pb[s])) return false;
+    const int d = sector_code(s) ^ sector_code((s + 1) & 7);  // neighbours differ in one compare
+    if (d != 1 && d != 2 && d != 4) return false;
+    seen |= 1u << sector_code(s);
+  }
+  return seen == 0xffu;  // a permutation of the 8 codes
+}
+static_assert(sector_code_ok(), "sector_code: the 8 sectors in circular order");
+
 // geo: the sphere table (P.sph).  The bounce-ray cluster cull of the later bounce rounds runs
 // whenever the launch has clusters (P.ncl > 0); without them the rounds test every sphere.
 // cullt: the pools' cull masks (P.cull), read by CULLC only; an argument of its own, read-only and
@@ -1082,6 +1115,8 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
   constexpr bool PL = C::PL, CLON = C::CLON, CNT = C::CNT, MF = C::MF, LAZY = C::LAZY, TAIL = C::TAIL, B1 = C::B1,
                  PT = C::PT, PTW = C::PTW, SORT = C::SORT, CULLC = C::CULLC;
   static_assert(!CULLC || !PL, "the cull table holds the spheres' masks only");
+  constexpr bool NSORT = C::NSORT;
+  static_assert(!NSORT || (CULLC && SORT), "the sort frames come with the cull table");
   __builtin_amdgcn_s_setprio(1);  // the pool's start at issue priority 1, back to 0 after the primary cull
   // CNT = false: the work counters compiled out (timed launches pass none): fewer live scalars
   unsigned long long* const cnts = CNT ? P.counters : nullptr;
@@ -1611,6 +1646,21 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
     // perm[] holds the cell table: it is free until the first prepare().
     constexpr int NC = kPool / 64, NF = 3;
     static_assert(NC * (1 << NF) <= 64, "one cell per lane");
+    // NSORT, launched with the pools' sort frames (P.cull_frames): the three bits are those of
+    // hemi's 45-degree sector around the pool's cached surface normal, a = dot(hemi, e1) < 0,
+    // b = dot(hemi, e2) < 0, |a| < |b| (NaN and -0 by the compares' results: any bin is valid), and
+    // the bins follow the sectors round the circle (sector_code).  (e1, e2): two scalar loads of
+    // the pool's row in front of the mask table, through the table's own argument.
+    bool framed = false;  // wave-uniform
+    f3 fe1 = mk(0.0f, 0.0f, 0.0f), fe2 = fe1;
+    if constexpr (NSORT) {
+      framed = P.cull_frames != 0;
+      if (framed) {
+        const float4* const fr = (const float4*)cullt - 2 * ((size_t)pb + 1);
+        fe1 = xyz(fr[0]);
+        fe2 = xyz(fr[1]);
+      }
+    }
     const int ln = lane_id_here();
     perm[ln] = 0;
     __syncthreads();
@@ -1643,14 +1693,27 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
         unsigned own_lo = (unsigned)mv, own_hi = (unsigned)(mv >> 32);
         unsigned oct = 0;  // bit k = sign bit of component k (as the ballots: -0 and NaN by their sign bit)
         const float hc[NF] = {h.x, h.y, h.z};
+        if (NSORT && framed) {
+          const float a = dot(h, fe1), b = dot(h, fe2);
+          const bool sb[NF] = {a < 0.0f, b < 0.0f, fabsf(a) < fabsf(b)};
 #pragma unroll
-        for (int k = NF - 1; k >= 0; --k) {
-          const int bits = __float_as_int(hc[k]);
-          const unsigned long long m = __ballot(bits < 0);
-          const unsigned sgn = (unsigned)(bits >> 31);
-          own_lo &= ~((unsigned)m ^ sgn);
-          own_hi &= ~((unsigned)(m >> 32) ^ sgn);
-          oct = oct << 1 | (unsigned)bits >> 31;
+          for (int k = NF - 1; k >= 0; --k) {
+            const unsigned long long m = __ballot(sb[k]);
+            const unsigned sgn = sb[k] ? ~0u : 0u;
+            own_lo &= ~((unsigned)m ^ sgn);
+            own_hi &= ~((unsigned)(m >> 32) ^ sgn);
+            oct = oct << 1 | (unsigned)sb[k];
+          }
+        } else {
+#pragma unroll
+          for (int k = NF - 1; k >= 0; --k) {
+            const int bits = __float_as_int(hc[k]);
+            const unsigned long long m = __ballot(bits < 0);
+            const unsigned sgn = (unsigned)(bits >> 31);
+            own_lo &= ~((unsigned)m ^ sgn);
+            own_hi &= ~((unsigned)(m >> 32) ^ sgn);
+            oct = oct << 1 | (unsigned)bits >> 31;
+          }
         }
         const int cell = (int)oct * NC + c;
         const int r = (int)__builtin_amdgcn_mbcnt_hi(own_hi, __builtin_amdgcn_mbcnt_lo(own_lo, 0u));
@@ -1662,8 +1725,12 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
     {  // lane = cell (bin ln / NC, chunk ln % NC) in sorted order: exclusive scan of the counts
       const int bin = ln / NC, c = ln % NC;
       const bool in = ln < NC * (1 << NF);
-      // bin b holds octant b ^ (b >> 1): Gray code, neighbouring bins' octants differ in one sign
-      const int cell = in ? (bin ^ (bin >> 1)) * NC + c : 0;
+      // bin b holds octant b ^ (b >> 1): Gray code, neighbouring bins' octants differ in one sign;
+      // framed: sector b's bits, the sectors in their order round the normal
+      int cell = in ? (bin ^ (bin >> 1)) * NC + c : 0;
+      if constexpr (NSORT) {
+        if (framed) cell = in ? sector_code(bin & 7) * NC + c : 0;
+      }
       const int n = in ? perm[cell] : 0;
       // inclusive scan on the DPP path: row_shr 1, 2, 4, 8 (zero fill) inside the rows of 16, then
       // row_bcast:15 into rows 1, 3 and row_bcast:31 into rows 2, 3
@@ -2315,6 +2382,15 @@ size_t tab_lds_bytes(const FrameParams& p) { return (size_t)5 * (p.nobj > 0 ? p.
 // i.e. the pool of pixels [pb TP, pb TP + np), so the table does not depend on the rotation).
 // One wave per pool and the kernel's own expressions, operand for operand (this file is built with
 // -ffp-contract=off), so the masks are the ones the pool would have computed, bit for bit.
+//
+// FRAMES: the pool's sort frame too, in front of the masks (FrameParams::cull_frames).  The ray is
+// the one prepare() forms for sample 0 (no jitter) of the pool's middle pixel, so while the masks
+// hold it holds; it meets the pool's surviving spheres in ascending order as prepare() does.  n0 is
+// the hit sphere's normal there, or the reversed ray when the middle pixel sees sky (a silhouette
+// pool); e1 = normalize(n0 x ref), e2 = n0 x e1, ref the x axis unless |n0.x| >= 0.9, then the y
+// axis.  Raw v_rsq: the frame orders the pool's samples and nothing else.  Every lane computes the
+// same values (one uniform ray), lane 0 stores them.
+template <bool FRAMES>
 __global__ __launch_bounds__(64) void cull_fill_kernel(FrameParams P, const float4* __restrict__ geo,
                                                        unsigned long long* __restrict__ table) {
   const int spp = P.spp, W = P.W, nobj = P.nobj;
@@ -2328,18 +2404,58 @@ __global__ __launch_bounds__(64) void cull_fill_kernel(FrameParams P, const floa
   const int yl = P.trace_row0 + (int)((p0 + np - 1) / W), xl = (int)((p0 + np - 1) % W);
   const int nwords = (nobj + 63) >> 6;
   const ConeF cone = pool_cone_f(P, yf == yl ? xf : 0, yf == yl ? xl : W - 1, yf, yl);
+  const f3 cam = mk(P.cx, P.cy, P.cz);
+  f3 dir = cam;
+  if (FRAMES) {  // pixel np / 2 of the pool, as the kernel's pool_xy and prepare() with aa == 0
+    int x = xf + np / 2, y = yf;
+    if (x >= W) {
+      const int q = (int)((unsigned)x / (unsigned)W);
+      y += q;
+      x -= q * W;
+    }
+    dir = primary_dir(P, div_rn_by((float)x + 0.0f, P.fW, P.inv_W), div_rn_by((float)y + 0.0f, P.fH, P.inv_H));
+  }
+  float t = -1.0f;
+  int ind = -1;
   for (int w = 0; w < nwords; ++w) {
     int i = (w << 6) + lane;
     bool keep = i < nobj && !cone_misses_f(cone, geo[i], P.cx, P.cy, P.cz);
     unsigned long long m = __ballot(keep);
     if (lane == 0) table[(size_t)pb * (unsigned)nwords + w] = m;
+    if (FRAMES) {
+      m = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(m >> 32)) << 32) |
+          (unsigned)__builtin_amdgcn_readfirstlane((unsigned)m);
+      while (m) {
+        const int j = pop_lowest(m);  // (j < 64 and bit j set only for (w << 6) + j < nobj)
+        sphere_candidate(cam, dir, geo[(w << 6) + j], (w << 6) + j, 0.0001f, t, ind);
+      }
+    }
+  }
+  if (FRAMES) {
+    f3 n0 = mk(-dir.x, -dir.y, -dir.z);
+    if (ind >= 0) {  // (wave-uniform)
+      const f3 v = (cam + t * dir) - xyz(geo[ind]);
+      n0 = fast_rsq(dot(v, v)) * v;
+    }
+    // n0 x ref: ref = (1, 0, 0), or (0, 1, 0) when n0 is within 26 degrees of the x axis
+    const bool ry = fabsf(n0.x) >= 0.9f;
+    const f3 c = ry ? mk(-n0.z, 0.0f, n0.x) : mk(0.0f, n0.z, -n0.y);
+    const f3 e1 = fast_rsq(dot(c, c)) * c;
+    const f3 e2 = mk(n0.y * e1.z - n0.z * e1.y, n0.z * e1.x - n0.x * e1.z, n0.x * e1.y - n0.y * e1.x);
+    if (lane == 0) {
+      float4* const fr = (float4*)table - 2 * ((size_t)pb + 1);
+      fr[0] = make_float4(e1.x, e1.y, e1.z, 0.0f);
+      fr[1] = make_float4(e2.x, e2.y, e2.z, 0.0f);
+    }
   }
 }
 
-hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, hipStream_t stream) {
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream) {
   const long long pools = ao_pool_count(p.trace_rows, p.W, p.spp);
   if (pools <= 0 || p.nobj <= 0) return hipSuccess;
-  hipLaunchKernelGGL(cull_fill_kernel, dim3((unsigned)pools), dim3(64), 0, stream, p, p.shapes + sphere_table(p.S), table);
+  const float4* const sph = p.shapes + sphere_table(p.S);
+  if (frames) hipLaunchKernelGGL(cull_fill_kernel<true>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
+  else hipLaunchKernelGGL(cull_fill_kernel<false>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
   return hipGetLastError();
 }
 
@@ -2420,6 +2536,14 @@ static_assert(ao_select(16, 20, 8, 64, 0, true, false, true) == AoChoice{16, 20,
 static_assert(ao_select(16, 20, 8, 64, 0, false, true, true) == AoChoice{16, 20, AO_CLON | kSortBit | AO_MF | AO_CULLC},
               "multi-frame cached");
 static_assert(ao_select(8, 20, 8, 64, 0, false, false, true) == AoChoice{0, 0, kSortBit | AO_CULLC}, "spp 8 cached");
+// the frame key: the cached, sorted, timed forms (multi-frame included); every other form the octant key
+static_assert(ao_sorts_by_frame(ao_select(16, 20, 8, 64, 0, false, false, true).flags) == (kSortBit != 0), "c, d cached");
+static_assert(ao_sorts_by_frame(ao_select(64, 20, 16, 256, 0, false, false, true).flags) == (kSortBit != 0), "e cached");
+static_assert(ao_sorts_by_frame(ao_select(16, 20, 8, 64, 0, false, true, true).flags) == (kSortBit != 0), "multi-frame cached");
+static_assert(!ao_sorts_by_frame(ao_select(16, 20, 8, 64, 0, true, false, true).flags), "counters cached: octants");
+static_assert(!ao_sorts_by_frame(ao_select(16, 20, 8, 64, 0, false, false, false).flags), "uncached: octants");
+static_assert(!ao_sorts_by_frame(ao_select(16, 20, 6, kB1SortMinObj - 1, 0, false, false, true).flags), "unsorted");
+static_assert(!ao_sorts_by_frame(ao_select(16, 20, 9, 65, 1, false, false, true).flags), "planes");
 static_assert(ao_select(16, 20, 9, 65, 1, false, false, true) == AoChoice{16, 0, AO_PL}, "p: never cached");
 static_assert(ao_select(4, 20, 0, 10, 1, false, false, true) == AoChoice{4, 0, AO_PL}, "ref: never cached");
 

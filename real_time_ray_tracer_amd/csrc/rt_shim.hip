@@ -95,6 +95,12 @@ constexpr int kSchedPeriod = 16;
 // Nothing waits on the host.  Pipelined AO passes alternate between streams: a stream's first
 // cached launch after a fill waits for the fill's event, and a refill waits for the events of
 // the last cached launches on every stream (recorded when the table was marked invalid).
+// Sort frames.  The fill also traces each pool's unjittered centre ray and keeps two unit vectors
+// orthogonal to the surface normal at its hit: 32 bytes per pool in front of the masks, in the same
+// allocation, so they share the masks' key, fill, events and invalidation.  The sorted cached
+// kernels deal a pool's samples by their sector around that normal (FrameParams::cull_frames).
+// When masks and frames together exceed the cap, or their allocation fails and the masks' alone
+// succeeds, the context keeps the masks only and the kernels their octant key.
 // Tables above kCullCacheMaxBytes are never built: those contexts, scenes with planes, and contexts
 // whose allocation failed keep the in-kernel cull.  The cap admits config (e)'s 265 MB (7680x4320,
 // 64 spp, 256 spheres: 8.3 M pools of 4 words, 1.5% of what that context's g-buffer ring holds),
@@ -107,6 +113,9 @@ constexpr int kCullRepeats = 2;  // launches in a row that must repeat a key bef
 struct CullCache {
   bool on = true;                    // rt_set_cull_cache
   bool nomem = false;                // the allocation failed once: never cached
+  size_t cap = kCullCacheMaxBytes;   // rt_debug_cull_cache_cap (test hook): this context's cap
+  void* d_alloc = nullptr;           // the allocation: frame_bytes of sort frames, then d_table
+  size_t frame_bytes = 0;            // 0: masks only
   unsigned long long* d_table = nullptr;
   size_t bytes = 0;                  // of d_table: pools x ceil(num_shapes / 64) words
   std::vector<unsigned char> key;    // the previous eligible launch's key
@@ -284,7 +293,7 @@ void free_sched(TileSched& h) {
 
 void free_all(rt_ctx* c) {
   for (auto& h : c->sched) free_sched(h);
-  if (c->cull.d_table) (void)hipFree(c->cull.d_table);
+  if (c->cull.d_alloc) (void)hipFree(c->cull.d_alloc);
   if (c->cull.ev_fill) (void)hipEventDestroy(c->cull.ev_fill);
   for (auto e : c->cull.ev_read)
     if (e) (void)hipEventDestroy(e);
@@ -475,10 +484,11 @@ bool cull_note(hipStream_t* set, hipStream_t st) {  // adds st; false if it was 
 int cull_before(rt_ctx* c, rt::FrameParams& p, hipStream_t st) {
   CullCache& k = c->cull;
   p.cull = nullptr;
+  p.cull_frames = 0;
   const int nwmax = (c->cfg.num_shapes + 63) / 64;
   const size_t need = (size_t)rt::ao_pool_count(p.trace_rows, p.W, p.spp) * nwmax * sizeof(unsigned long long);
   const bool whole_band = p.trace_row0 == c->band0 && p.trace_rows == c->band_rows;  // (every AO launch's rows)
-  if (!k.on || k.nomem || p.nplanes > 0 || p.nobj <= 0 || !whole_band || need == 0 || need > kCullCacheMaxBytes) {
+  if (!k.on || k.nomem || p.nplanes > 0 || p.nobj <= 0 || !whole_band || need == 0 || need > k.cap) {
     k.have_key = false;
     return cull_invalidate(c);
   }
@@ -498,19 +508,30 @@ int cull_before(rt_ctx* c, rt::FrameParams& p, hipStream_t st) {
   k.repeats = kCullRepeats;
   if (!k.valid) {
     if (!k.d_table) {  // lazily; a failed allocation leaves the context uncached
-      const hipError_t e = hipMalloc(&k.d_table, need);
+      // masks and sort frames in one allocation when both fit the cap, else (or when that
+      // allocation fails) the masks alone
+      size_t fb = rt::ao_cull_frame_bytes(rt::ao_pool_count(p.trace_rows, p.W, p.spp));
+      if (fb > k.cap - need) fb = 0;
+      hipError_t e = hipMalloc(&k.d_alloc, fb + need);
+      if (e != hipSuccess && fb != 0) {
+        (void)hipGetLastError();
+        fb = 0;
+        e = hipMalloc(&k.d_alloc, need);
+      }
       if (e != hipSuccess) {
         (void)hipGetLastError();
-        k.d_table = nullptr;
+        k.d_alloc = nullptr;
         k.nomem = true;
         return RT_OK;
       }
+      k.frame_bytes = fb;
+      k.d_table = (unsigned long long*)((char*)k.d_alloc + fb);
       k.bytes = need;
     }
     if (!k.ev_fill) RT_HIP(c, hipEventCreateWithFlags(&k.ev_fill, hipEventDisableTiming));
     for (int s = 0; s < k.n_read; ++s) RT_HIP(c, hipStreamWaitEvent(st, k.ev_read[s], 0));
     k.n_read = 0;
-    const hipError_t e = rt::launch_cull_fill(p, k.d_table, st);
+    const hipError_t e = rt::launch_cull_fill(p, k.d_table, k.frame_bytes != 0, st);
     if (e != hipSuccess) return hip_fail(c, e);
     RT_HIP(c, hipEventRecord(k.ev_fill, st));
     for (auto& s : k.seen) s = nullptr;
@@ -521,6 +542,7 @@ int cull_before(rt_ctx* c, rt::FrameParams& p, hipStream_t st) {
   if (cull_note(k.seen, st)) RT_HIP(c, hipStreamWaitEvent(st, k.ev_fill, 0));
   cull_note(k.readers, st);
   p.cull = k.d_table;
+  p.cull_frames = k.frame_bytes != 0;
   k.cached += 1;
   return RT_OK;
 }
@@ -1485,6 +1507,15 @@ int rt_set_cull_cache(rt_ctx* c, int on) {
   c->cull.have_key = false;  // on again: the key has to hold anew
   return cull_invalidate(c);
 }
+
+int rt_debug_cull_cache_cap(rt_ctx* c, size_t bytes) {
+  if (!c) return RT_E_INVAL;
+  if (c->cull.d_alloc) return RT_E_INVAL;  // before the first fill
+  c->cull.cap = bytes && bytes < kCullCacheMaxBytes ? bytes : kCullCacheMaxBytes;
+  return RT_OK;
+}
+
+size_t rt_cull_cache_frame_bytes(rt_ctx* c) { return c ? c->cull.frame_bytes : 0; }
 
 int rt_cull_cache_stats(rt_ctx* c, long long* fills, long long* cached_launches, size_t* table_bytes) {
   if (!c) return RT_E_INVAL;

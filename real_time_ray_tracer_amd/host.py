@@ -276,6 +276,14 @@ class Renderer:
         self._c(self._lib.rt_cull_cache_stats(self.ctx, C.byref(f), C.byref(n), C.byref(b)), "rt_cull_cache_stats")
         return {"fills": f.value, "cached_launches": n.value, "table_bytes": b.value}
 
+    def cull_cache_frame_bytes(self) -> int:
+        """Bytes of the pools' sort frames kept with the masks (rt_cull_cache_frame_bytes); 0: masks only."""
+        return int(self._lib.rt_cull_cache_frame_bytes(self.ctx))
+
+    def debug_cull_cache_cap(self, nbytes: int):
+        """Test hook (rt_debug_cull_cache_cap): this context's cap on the cull cache, before its first fill."""
+        self._c(self._lib.rt_debug_cull_cache_cap(self.ctx, int(nbytes)), "rt_debug_cull_cache_cap")
+
     def download(self, pixels=True, normals=True, depth=True, image=True) -> GBuffer:
         shp = (self.F, self.W, self.R, 4)
         p = np.empty(shp, np.float32) if pixels else None

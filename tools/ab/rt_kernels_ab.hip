@@ -152,6 +152,9 @@ using ProdECounted = AoProd<64, kRefDepth, AO_CLON | AO_WIDE | AO_CNT>;  // conf
 using Counted16 = AoProd<16, 0, AO_CNT>;                            // spp 16, any depth, with counters
 using Counted16Sorted = AoProd<16, 0, AO_CNT | AO_SORT>;
 using PlaneCounted16 = AoProd<16, 0, AO_PL | AO_CNT>;
+// Counted16Sorted on a cached launch, keyed on the pools' sort frames as the timed cached forms are
+// (production's counter forms keep the octant key): the event counts of the sector key
+struct Counted16Framed : AoProd<16, 0, AO_CNT | AO_SORT | AO_CULLC> { static constexpr bool NSORT = true; };
 struct NoPretest : AoProd<16, 0, 0> { static constexpr bool PT = false; };
 struct NoLazy : AoConfig { static constexpr bool LAZY = false; };
 struct NoFirstBounce : AoConfig { static constexpr bool TAIL = true; };  // (so no pre-test: the table stays in the LDS rows' place)
@@ -165,7 +168,9 @@ struct Abl : B { static constexpr int ABL = A; };  // B with diagnostic A (ao_ba
 // RTRT_AO_VARIANT selects an experimental AO kernel per launch: 9 (no first-bounce pre-test),
 // 27 (no batched first bounce), 17 (no split tail rounds), 11 (no lazy shortcuts), 91-93 (timing
 // ablations: bounce tests twice, culled primary tests twice, section clocks), 96/97 (section
-// clocks with the first bounce split, event counts), 0/2 (the lane-per-sample kernel, LDS table /
+// clocks with the first bounce split, event counts; 197 / 297: 97 sorted by octant / by the sectors
+// around the pool's cached normal, the latter on launches that have the table), 0/2 (the
+// lane-per-sample kernel, LDS table /
 // scalar table).  RTRT_GENERAL=1 runs every program on the unculled LDS-table kernels (the pre-plane-
 // support path for scenes with planes).  RTRT_B1_MIN: least live lanes for a batched first bounce.
 static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t stream, long long npix) {
@@ -194,6 +199,7 @@ static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t strea
     return true;
   }
   if (variant == 7 || (p.nplanes > 0 && variant != 93)) return false;  // production
+  if (variant == 297 && !(q.cull && q.cull_frames)) return false;      // (until the table is filled)
   // every variant's LDS rows after the layout: ntail float4 (the sphere table where the variant stages it)
   auto go = [&](auto cfg, int ntail) {
     using C = decltype(cfg);
@@ -248,6 +254,8 @@ static bool ab_launch_ao(const FrameParams& p, FrameParams& q, hipStream_t strea
     go(Abl<Counted16, 7>{}, ntail);
   else if (variant == 197 && tl && p.spp == 16)  // 97 with the pool's samples sorted by hemi's octant (AoConfig::SORT)
     go(Abl<Counted16Sorted, 7>{}, p.nobj);
+  else if (variant == 297 && tl && p.spp == 16)  // 197 with the sort keyed on the pool's cached frame
+    go(Abl<Counted16Framed, 7>{}, p.nobj);
   else if (variant == 93 && tl && p.spp == 16)  // section clocks of the production kernel
     go(Abl<Counted16, 3>{}, ntail);
   else if (variant == 93 && tl)

@@ -10,9 +10,13 @@ no parity claim (results cannot depend on the order: every sample's path is a fu
 Keys (hemi = get_pt_within_unit_sphere(aa, pixel), known before any primary ray):
   item      today's order
   oct8      hemi's octant, the 8 bins in Gray-code order (neighbours differ in one sign); no axis
-  az8/az16  azimuth of hemi around n0 in 8 / 16 sectors; n0 = the normal at the pool's first live
+  az8/az16  the cached kernels' key: hemi's 45 / 22.5 degree sector around n0, counted from e1 towards
+            e2 (e1 = normalize(n0 x ref), e2 = n0 x e1); n0 = the normal where the unjittered ray of
+            the pool's middle pixel hits (emissive or not), the reversed ray when it misses
+            (cull_fill_kernel's frame)
+  faz8/faz16  the round-7 model: sectors counted from -pi, n0 = the normal at the pool's first live
             unjittered sample (first live sample when no pixel centre hits; oct8 when none is live)
-  azdir     bound: the true bounce direction's azimuth around n0, continuous
+  azdir     bound: the true bounce direction's azimuth around that n0, continuous
 
     python tools/explore/b1_sort_sim.py --config d --rows 12
 """
@@ -38,13 +42,14 @@ POOL = 256
 
 
 def row_states(fr: nr.Frame, y: int):
-    """b1_pairs_sim.first_bounce_states plus, per sample, hemi and the primary hit's normal."""
+    """b1_pairs_sim.first_bounce_states plus, per sample, hemi and the primary hit's normal, and per
+    pixel the axis of its unjittered ray (the hit's normal, or the reversed ray)."""
     W, AA = fr.W, fr.AA
     x = np.arange(W)
     px, py = x.astype(F), np.full(W, y, F)
     cam = fr.hdr[4, :3]
     P = np.zeros((W, AA, 3)); Dn = np.zeros((W, AA, 3)); L = np.zeros((W, AA), bool)
-    Hm = np.zeros((W, AA, 3)); N = np.zeros((W, AA, 3))
+    Hm = np.zeros((W, AA, 3)); N = np.zeros((W, AA, 3)); Nax = np.zeros((W, 3))
     for aa in range(AA):
         fst, snd = fr.rb[2 * aa], fr.rb[2 * aa + 1]
         if aa == 0:
@@ -63,6 +68,11 @@ def row_states(fr: nr.Frame, y: int):
         pos = np.broadcast_to(cam, (W, 3)).astype(F)
         t, ind = fr.closest(pos, dirs, 0.0001)
         hit = ind >= 0
+        if aa == 0:
+            Nax[:] = -dirs
+            hi = np.nonzero(hit)[0]
+            if hi.size:
+                Nax[hi] = fr.normal(ind[hi], cam + t[hi, None] * dirs[hi])
         emis = np.zeros(W, bool)
         emis[hit] = fr.shapes[ind[hit], 1, 3] > F(0.9)
         ci = np.nonzero(hit & ~emis)[0]
@@ -83,7 +93,7 @@ def row_states(fr: nr.Frame, y: int):
             Dn[ci, aa] = nd
             L[ci, aa] = True
             N[ci, aa] = nn
-    return P.reshape(-1, 3), Dn.reshape(-1, 3), L.reshape(-1), Hm.reshape(-1, 3), N.reshape(-1, 3)
+    return P.reshape(-1, 3), Dn.reshape(-1, 3), L.reshape(-1), Hm.reshape(-1, 3), N.reshape(-1, 3), Nax
 
 
 def oct8(h):
@@ -112,12 +122,20 @@ def azimuth(v, n0):
     return np.arctan2((v * e2[:, None]).sum(2), (v * e1[:, None]).sum(2))  # [-pi, pi]
 
 
-def keys(name, Hm, Dn, L, N, AA):
+def keys(name, Hm, Dn, L, N, AA, Nax):
     npool = Hm.shape[0]
     if name == "item":
         return np.zeros((npool, POOL))
     if name == "oct8":
         return oct8(Hm).astype(np.float64)
+    if name in ("az8", "az16"):  # the kernel's: the frame of the pool's middle pixel, sector 0 starts at e1
+        tp = POOL // AA
+        n0 = Nax[np.arange(npool) * tp + tp // 2]
+        nb = int(name[2:])
+        ang = np.mod(azimuth(Hm, n0), 2 * np.pi)
+        return np.minimum(np.floor(ang / (2 * np.pi) * nb), nb - 1)
+    if name in ("faz8", "faz16"):
+        name = name[1:]
     if name == "octz":  # the Gray code's fastest bit on z (the view axis of the bench configs)
         return oct8(Hm[..., [2, 0, 1]]).astype(np.float64)
     n0, ok = pool_axis(L, N, AA)
@@ -138,7 +156,7 @@ def main():
     ap.add_argument("--config", default="d")
     ap.add_argument("--rows", type=int, default=12)
     ap.add_argument("--seed", type=int, default=5)
-    ap.add_argument("--keys", default="item,oct8,az8,az16,azdir")
+    ap.add_argument("--keys", default="item,oct8,az8,az16,faz8,azdir")
     a = ap.parse_args()
     W, H, S, spp, mode, _ = CONFIGS[a.config]
     h = config_header(a.config)
@@ -152,12 +170,12 @@ def main():
     names = a.keys.split(",")
     tot = {n: dict(b1=0, kept=0, passing=0, defer=0, live=0, pairs=0) for n in names}
     for y in rows:
-        P, Dn, L, Hm, N = row_states(fr, int(y))
+        P, Dn, L, Hm, N, Nax = row_states(fr, int(y))
         npool = P.shape[0] // POOL
         cut = lambda v: v[:npool * POOL].reshape(npool, POOL, *v.shape[1:])  # noqa: E731
         P, Dn, L, Hm, N = cut(P), cut(Dn), cut(L), cut(Hm), cut(N)
         for n in names:
-            order = np.argsort(keys(n, Hm, Dn, L, N, fr.AA), axis=1, kind="stable")
+            order = np.argsort(keys(n, Hm, Dn, L, N, fr.AA, Nax), axis=1, kind="stable")
             g = lambda v: np.take_along_axis(v, order[..., None] if v.ndim == 3 else order, 1)  # noqa: E731
             masks, keepb, nl, nk, _ = batch_masks(g(P).reshape(-1, 3), g(Dn).reshape(-1, 3), g(L).reshape(-1), geo)
             d, _, q, ps = count(masks[keepb])

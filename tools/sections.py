@@ -6,6 +6,7 @@
     python tools/sections.py --config d --variant 96   # the first bounce split into cull / survivors / shade
     python tools/sections.py --config d --variant 97   # event counts: first-bounce survivors, bounce-round tails
     python tools/sections.py --config d --variant 197  # 97 with RT_B1_SORT's sorted pools
+    python tools/sections.py --config d --variant 297  # 197 keyed on the pool's cached normal (frame 3 is the first cached)
     python tools/sections.py --config d --variant 98   # full bounce rounds and split tail rounds apart
     python tools/sections.py --config e --variant 193  # (e)'s instantiation (196, 198 as 96, 98)
 """
@@ -46,7 +47,7 @@ def main():
     c = r.read_counters()
     keys = ["samples", "segments", "shadow_rays", "tests", "executed_lane_tests", "filtered_pixels", "history_read",
             "history_accepted"]
-    if a.variant in ("97", "197"):  # 197: with the pool's samples sorted by bounce direction (RT_B1_SORT)
+    if a.variant in ("97", "197", "297"):  # 197 / 297: the pool's samples sorted by octant / by sector round its normal
         v = [c[k] for k in keys]
         print(f"first bounce: {v[4]} batches, {v[5] / max(v[4], 1):.1f} live lanes per batch, "
               f"{v[0] / max(v[4], 1):.2f} survivor iterations per batch")
