@@ -314,7 +314,12 @@ class Frame:
         col = np.concatenate([np.power(acc[:, :3], GAMMA), np.zeros((n, 1), F)], 1).astype(F)
         self.store(x, y, col, image if write_image else None, gy0)
 
-    def aop_postprocessing(self, x, y, image, gy0, gh):
+    def aop_postprocessing(self, x, y, image, gy0, gh, stats=None):
+        """stats: an optional dict, filled per pixel (in the order of x, y) with what the filter did:
+        x, y, filtered (own w > 0.99), weights [n][4] (up, down, left, right; 0 for an absent
+        neighbour), den, coeff [n][F-1] (the history coefficient of slots f-1, f-2, ... whether or
+        not the loop got there), accepted (slots summed) and visited (slots tested: accepted, plus
+        the one that failed).  Every figure but `filtered` is meaningful for filtered pixels only."""
         f, Fn, W, H = self.frame, self.F, self.W, self.H
         snap = self.pix[f].copy()
         gy = y - gy0
@@ -339,14 +344,17 @@ class Frame:
         nbrs = [(x, y + 1, y + 1 < H), (x, y - 1, y >= 2), (x - 1, y, x > 0), (x + 1, y, x + 1 < W)]
         acc = color.copy()
         den = np.ones(len(x), F)
+        weights = []
         for xx, yy, pr in nbrs:
             wv, kv = weight(xx, yy, pr)
+            weights.append(wv)
             acc = (acc + wv[:, None] * kv).astype(F)
             den = (den + wv).astype(F)
         sp = (acc / den[:, None]).astype(F)
         cs = np.zeros((len(x), 4), F)
         denom = np.full(len(x), F(0.9))
         go = np.ones(len(x), bool)
+        coeffs, accepted = [], np.zeros(len(x), np.int64)
         for i in range(1, Fn):
             cf = (f + Fn - i) % Fn
             hn, hd = self.nrm[cf, x, gy], self.dep[cf, x, gy]
@@ -354,14 +362,21 @@ class Frame:
             bd = F(1.0) - clamp(np.abs(nb - hd[:, 1]) / F(1.7), 0.0, 1.0)
             coeff = (dot3(nv, hn[:, :3]) * dd * bd).astype(F)
             go &= coeff > F(0.85)
+            coeffs.append(coeff)
+            accepted += go
             cs = np.where(go[:, None], cs + coeff[:, None] * self.pix[cf, x, gy], cs).astype(F)
             denom = np.where(go, denom + coeff, denom).astype(F)
         filt = ((sp * F(0.9) + cs) / denom[:, None]).astype(F)
         out = np.where(active[:, None], filt, color)
+        if stats is not None:
+            stats.update(x=x, y=y, filtered=active, weights=np.stack(weights, 1), den=den,
+                         coeff=np.stack(coeffs, 1) if coeffs else np.zeros((len(x), 0), F), accepted=accepted,
+                         visited=np.minimum(accepted + 1, Fn - 1))
         self.store(x, y, out, image, gy0)
 
 
-def run_program(ssbo, W, H, S, AA, program, frame, image=None, F_=8, D=20, gy0=0, gh=None, y0=None, y1=None):
+def run_program(ssbo, W, H, S, AA, program, frame, image=None, F_=8, D=20, gy0=0, gh=None, y0=None, y1=None,
+                stats=None):
     gh = H if gh is None else gh
     ssbo[1] = F(frame)
     fr = Frame(ssbo, W, gh, S, AA, F_, D)
@@ -377,7 +392,7 @@ def run_program(ssbo, W, H, S, AA, program, frame, image=None, F_=8, D=20, gy0=0
     elif program in (AO_COMPUTE, AOP_COMPUTE):
         fr.ao_compute(x, y, image, gy0, program == AO_COMPUTE)
     elif program == AOP_POSTPROCESSING:
-        fr.aop_postprocessing(x, y, image, gy0, gh)
+        fr.aop_postprocessing(x, y, image, gy0, gh, stats)
     else:
         raise ValueError(program)
 

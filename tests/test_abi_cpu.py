@@ -207,6 +207,9 @@ def post_tile_run(W: int) -> int:
 
 @pytest.mark.parametrize("W,H", [(3840, 2160), (1920, 1080), (7680, 4320), (440, 330), (640, 480), (200, 150)])
 def test_post_tile_order_is_a_bijection_with_xcd_local_neighbours(W, H):
+    """The run map of xcd_tile as a function over arbitrary grids (here the grids 16 x 16 tiles
+    would give), not the production geometry: a tile is 64 x 4 pixels now and launch_params prefers
+    super-tiles, both restated and checked in tests/test_post_synthetic_cpu.py."""
     gx, gy = (W + 15) // 16, (H + 15) // 16
     R = post_tile_run(W)
     m = [post_tile_of_block(L, gx, gy, R) for L in range(gx * gy)]
