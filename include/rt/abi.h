@@ -22,7 +22,7 @@
  *   - all GPU work is ordered on the context's HIP stream (rt_set_stream to share one).
  *
  * Host-only helpers (rt_pack_*, rt_camera_basis, rt_fill_rand_buffer, rt_moving_light,
- * rt_scenegen, rt_init_scene, rt_strerror, rt_version) never touch the GPU.
+ * rt_scenegen, rt_init_scene, rt_quantize_rgba8, rt_strerror, rt_version) never touch the GPU.
  */
 #ifndef RT_ABI_H
 #define RT_ABI_H
@@ -199,6 +199,33 @@ void* rt_image_device_ptr(rt_ctx* ctx);
 /* Render the image into a caller-owned device buffer of R*W float4 (NULL = own buffer). */
 int rt_bind_image(rt_ctx* ctx, void* device_ptr);
 
+/* ---- 8-bit display output (the blit, src/main.cpp:783-797) -------------------------- */
+/* The reference ends a frame by drawing the rgba32f image into an 8-bit framebuffer
+ * (src/main.cpp:783-797 through resources/shader_fragment.glsl:9-19: colour unchanged, alpha 1).
+ * The conversion, per channel v of r, g, b in binary32 without contraction: NaN -> 0, v <= 0 -> 0,
+ * v >= 1 -> 255, else (uint8)(v * 255.0f + 0.5f) truncated; the alpha byte is 255; bytes in r, g,
+ * b, a order.  top_down = 0: output row j is image row j (row 0 = bottom row, like the image);
+ * top_down != 0: output row j is image row R - 1 - j, the order a window or a PPM wants (for a
+ * strip context R is the strip's rows and the flip is within the strip).  All opt-in: a context
+ * that never calls these allocates nothing and launches nothing. */
+/* Replaces the blit: enqueue the conversion of the current image (the context's own or the one
+ * given to rt_bind_image) on rt_image_stream(ctx), so it reads the image after the launch that
+ * wrote it and the next image writer is ordered after it.  It creates no stream and no event, and
+ * returns without waiting.  The context's own 8-bit buffer is allocated (and zeroed) by the first
+ * present that needs it. */
+int rt_present(rt_ctx* ctx, int top_down);
+/* Where the last rt_present wrote: [R][W] RGBA8 on the device; NULL before the first present. */
+void* rt_present_device_ptr(rt_ctx* ctx);
+/* Later presents write into a caller-owned device buffer of R*W*4 bytes, 4-byte aligned (16-byte
+ * aligned for the 16-byte stores); NULL = the context's own buffer.  Does not wait for anything:
+ * presents already enqueued write where they were told to. */
+int rt_bind_present(rt_ctx* ctx, void* device_ptr);
+/* The blit plus glReadPixels: rt_present, wait (as rt_download does), copy R*W*4 bytes to `out`. */
+int rt_download_rgba8(rt_ctx* ctx, int top_down, uint8_t* out);
+/* Host-only: the same conversion of image = [rows][width] rgba32f into out = [rows][width][4].  The
+ * specification of rt_present in C; never touches the GPU. */
+int rt_quantize_rgba8(const float* image, int width, int rows, int top_down, uint8_t* out);
+
 /* ---- host-buffer parity path (mirrors the reference call shape) -------------------- */
 /* compute_one_shader(frame_num, prog) (src/main.cpp:580-620): sets mode.y = frame_num in
  * `ssbo` (a whole ssbo_data-layout host buffer of rt_ssbo_bytes(S,spp,W,R,F) bytes), copies
@@ -296,6 +323,19 @@ int rt_group_strip_device(rt_group* g, int i);
  * and its root strip come from the second round on, so rounds >= 2. */
 int rt_group_set_link_model(rt_group* g, double link_gbps, double ingest_gbps);
 int rt_group_link_model(rt_group* g, double* link_gbps, double* ingest_gbps);
+/* 8-bit output of the group (the blit of the whole frame, src/main.cpp:783-797), off by default.
+ * While on, the group keeps an [H][W] RGBA8 frame on devices[0] and every strip's frame is followed
+ * by rt_present on that strip: a strip that renders into the frame presents straight into its rows
+ * of the 8-bit frame, every other strip copies its 8-bit strip (rows * W * 4 bytes, a quarter of
+ * the float strip) on rt_image_stream in place of the float copy.  With top_down, strip i lands at
+ * rows [H - bounds[i+1], H - bounds[i]).  The float frame is then no longer assembled
+ * (rt_group_download_image returns RT_E_STATE), and rt_group_balance plans the copies at a quarter
+ * of the bytes.  on = 0 restores the float assembly exactly.  Waits for the frames in flight. */
+int rt_group_enable_rgba8(rt_group* g, int on, int top_down);
+/* The assembled [H][W] RGBA8 frame (RT_E_STATE while 8-bit output is off). */
+int rt_group_download_rgba8(rt_group* g, uint8_t* out);
+/* The 8-bit frame on devices[0]; NULL while 8-bit output is off. */
+void* rt_group_rgba8_device_ptr(rt_group* g);
 /* Rescale row_cost so every strip's total equals its measured time (row shape kept). */
 int rt_calibrate_row_cost(double* row_cost, int H, const int* bounds, int n, const double* strip_ms);
 

@@ -71,6 +71,14 @@ SIGNATURES = {
     "rt_upload_gbuffer": (C.c_int, [_ctx, _fp, _fp, _fp]),
     "rt_image_device_ptr": (_vp, [_ctx]),
     "rt_bind_image": (C.c_int, [_ctx, _vp]),
+    "rt_present": (C.c_int, [_ctx, C.c_int]),
+    "rt_present_device_ptr": (_vp, [_ctx]),
+    "rt_bind_present": (C.c_int, [_ctx, _vp]),
+    "rt_download_rgba8": (C.c_int, [_ctx, C.c_int, _vp]),
+    "rt_quantize_rgba8": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _vp]),
+    "rt_group_enable_rgba8": (C.c_int, [_grp, C.c_int, C.c_int]),
+    "rt_group_download_rgba8": (C.c_int, [_grp, _vp]),
+    "rt_group_rgba8_device_ptr": (_vp, [_grp]),
     "rt_compute_one_shader": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, _fp]),
     "rt_compute_two_shaders": (C.c_int, [_ctx, _vp, C.c_int, C.c_int, C.c_int, _fp]),
     "rt_group_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(rt_config), C.POINTER(C.c_int),

@@ -12,6 +12,9 @@
 //     pipelined mode-1 frame, the main stream otherwise), so frame k's copy follows that pass
 //     and overlaps frame k+1's trace passes; the next pass that writes the image is ordered
 //     after everything on that stream, the copy included.
+// With 8-bit output on (rt_group_enable_rgba8) every strip's frame is followed by rt_present, the
+// blit's conversion, and what is assembled is an [H][W] RGBA8 frame: the same two paths with a
+// quarter of the bytes on the links (finish_strip).
 // Each strip keeps its own g-buffer ring for its rows plus a 1-row halo (rt_create), so no
 // strip reads another's data: the copies into the frame are the only transfers.
 // One host thread per strip enqueues its strip's work, so the per-frame host cost does not add
@@ -123,6 +126,11 @@ struct rt_group {
   // runs on devices[i + 1], strip i > root on devices[i] (root 0: strip i on devices[i])
   int root = 0;
   double link_gbps = 0.0, ingest_gbps = 0.0;  // the gather-aware planner's link model (0: measure)
+  // 8-bit output (rt_group_enable_rgba8): every strip's frame is followed by rt_present, and the
+  // strips' RGBA8 rows are assembled in frame8 in place of the float rows in `frame`
+  bool rgba8 = false;
+  bool top_down = false;
+  unsigned char* frame8 = nullptr;  // [H][W][4] on devices[0] while rgba8
 };
 
 namespace {
@@ -145,10 +153,19 @@ void destroy_strips(rt_group* g) {
     }
 }
 
+// strip i's rows of the 8-bit frame: rows [bounds[i], bounds[i+1]), or, top down, the frame flipped:
+// rows [H - bounds[i+1], H - bounds[i]) (each strip's present flips within the strip)
+unsigned char* strip_rows8(const rt_group* g, int i) {
+  const int row = g->top_down ? g->cfg.height - g->bounds[i + 1] : g->bounds[i];
+  return g->frame8 + (size_t)row * g->cfg.width * 4;
+}
+
 int bind_strips(rt_group* g) {
   const int W = g->cfg.width;
   for (int i = 0; i < g->n; ++i) {
     int rc = rt_bind_image(g->ctx[i], on_root(g, i) ? (void*)(g->frame + (size_t)g->bounds[i] * W) : nullptr);
+    // 8-bit output: the strips that render into the frame present into the 8-bit frame as well
+    if (rc == RT_OK) rc = rt_bind_present(g->ctx[i], g->rgba8 && on_root(g, i) ? (void*)strip_rows8(g, i) : nullptr);
     if (rc != RT_OK) return rc;
   }
   return RT_OK;
@@ -191,8 +208,27 @@ int copy_strip(rt_group* g, int i) {
   return RT_OK;
 }
 
+// What follows every frame of strip i: the float copy above, or with 8-bit output on the strip's
+// present (the blit, src/main.cpp:783-797) and, for a strip off the frame, the copy of its
+// rows * W * 4 bytes instead.  Both go on the stream that wrote the image, like copy_strip's.
+int finish_strip(rt_group* g, int i) {
+  if (!g->rgba8) return copy_strip(g, i);
+  int rc = rt_present(g->ctx[i], g->top_down);
+  if (rc != RT_OK || on_root(g, i)) return rc;
+  const size_t bytes = (size_t)(g->bounds[i + 1] - g->bounds[i]) * g->cfg.width * 4;
+  hipError_t e = hipSetDevice(strip_dev(g, i));
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(strip_rows8(g, i), rt_present_device_ptr(g->ctx[i]), bytes, hipMemcpyDeviceToDevice,
+                       (hipStream_t)rt_image_stream(g->ctx[i]));
+  if (e != hipSuccess) {
+    g->last_hip = (int)e;
+    return RT_E_HIP;
+  }
+  return RT_OK;
+}
+
 // n frames of the render loop (src/main.cpp:763-781) on strip i, as rt_compute_frames does,
-// each followed by the strip's copy into the frame.
+// each followed by the strip's copy into the frame (finish_strip).
 int strip_frames(rt_group* g, int i, float* hdr, int mode, int frame, int n, uint64_t seed, int light) {
   const int S = g->cfg.num_shapes, spp = g->cfg.spp;
   const size_t bytes = rt_header_bytes(S, spp);
@@ -207,7 +243,7 @@ int strip_frames(rt_group* g, int i, float* hdr, int mode, int frame, int n, uin
     if (rc != RT_OK) return rc;
     frame = rt_dispatch(g->ctx[i], mode, frame);
     if (frame < 0) return frame;
-    rc = copy_strip(g, i);
+    rc = finish_strip(g, i);
     if (rc != RT_OK) return rc;
   }
   return frame;
@@ -503,6 +539,10 @@ int rt_group_destroy(rt_group* g) {
     (void)hipSetDevice(g->devices[0]);
     (void)hipFree(g->frame_own);
   }
+  if (g->frame8) {
+    (void)hipSetDevice(g->devices[0]);
+    (void)hipFree(g->frame8);
+  }
   delete g;
   return RT_OK;
 }
@@ -598,7 +638,7 @@ int rt_group_dispatch(rt_group* g, int mode, int frame) {
     }
     int f = rt_dispatch(g->ctx[i], mode, frame);
     if (f < 0) return f;
-    return copy_strip(g, i);
+    return finish_strip(g, i);
   });
   if (rc != RT_OK) return rc;
   return (frame + 1) % g->cfg.num_frames;
@@ -635,8 +675,52 @@ int rt_group_synchronize(rt_group* g) {
   return RT_OK;
 }
 
+int rt_group_enable_rgba8(rt_group* g, int on, int top_down) {
+  if (!g) return RT_E_INVAL;
+  int rc = rt_group_synchronize(g);  // the frames in flight still write the frame in use
+  if (rc != RT_OK) return rc;
+  const size_t bytes = (size_t)g->cfg.height * g->cfg.width * 4;
+  hipError_t e = hipSetDevice(g->devices[0]);
+  if (e == hipSuccess && on && !g->frame8) {
+    e = hipMalloc(&g->frame8, bytes);
+    if (e == hipSuccess) e = hipMemset(g->frame8, 0, bytes);
+    if (e != hipSuccess && g->frame8) {
+      (void)hipFree(g->frame8);
+      g->frame8 = nullptr;
+    }
+  }
+  if (e == hipSuccess && !on && g->frame8) {
+    e = hipFree(g->frame8);
+    g->frame8 = nullptr;
+  }
+  if (e != hipSuccess) {
+    g->last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_HIP;
+  }
+  g->rgba8 = on != 0;
+  g->top_down = on && top_down;
+  return bind_strips(g);
+}
+
+int rt_group_download_rgba8(rt_group* g, uint8_t* out) {
+  if (!g || !out) return RT_E_INVAL;
+  if (!g->rgba8) return RT_E_STATE;
+  int rc = rt_group_synchronize(g);
+  if (rc != RT_OK) return rc;
+  hipError_t e = hipSetDevice(g->devices[0]);
+  if (e == hipSuccess) e = hipMemcpy(out, g->frame8, (size_t)g->cfg.height * g->cfg.width * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    g->last_hip = (int)e;
+    return RT_E_HIP;
+  }
+  return RT_OK;
+}
+
+void* rt_group_rgba8_device_ptr(rt_group* g) { return g && g->rgba8 ? (void*)g->frame8 : nullptr; }
+
 int rt_group_download_image(rt_group* g, float* image) {
   if (!g || !image) return RT_E_INVAL;
+  if (g->rgba8) return RT_E_STATE;  // the float frame is not assembled while 8-bit output is on
   int rc = rt_group_synchronize(g);
   if (rc != RT_OK) return rc;
   hipError_t e = hipSetDevice(g->devices[0]);
@@ -757,6 +841,10 @@ int rt_group_balance(rt_group* g, const float* header, int mode, int rounds, dou
   // re-plans the calibrated (ms) profile with the link model, measured here unless set.
   bool gather = g->force_copies;
   for (int i = 1; i < n; ++i) gather = gather || g->devices[i] != g->devices[0];
+  // with 8-bit output on, a strip sends rows * W * 4 bytes, not the 16 B per pixel the planner
+  // counts: the same bound with four times the link and ingest rates (the rates themselves were
+  // measured on float-sized copies, probe_links)
+  const double bytes_scale = g->rgba8 ? 4.0 : 1.0;
   // 2. calibration: time every strip of the plan alone, as the frame loop renders it (wall
   // clock of 16 frames after 8, gather copy included), rescale the profile so each strip's
   // total is its time, re-plan; keep the plan with the smallest bound (measured render, the link
@@ -789,7 +877,8 @@ int rt_group_balance(rt_group* g, const float* header, int mode, int rounds, dou
       std::vector<double> per_row(H, 0.0);  // the measured strip times spread over their rows
       for (int i = 0; i < n; ++i)
         for (int y = b[i]; y < b[i + 1]; ++y) per_row[y] = t[i] / (b[i + 1] - b[i]);
-      rc = rt_strip_gather_bound(per_row.data(), H, b.data(), n, root, W, g->link_gbps, g->ingest_gbps, bound);
+      rc = rt_strip_gather_bound(per_row.data(), H, b.data(), n, root, W, bytes_scale * g->link_gbps,
+                                 bytes_scale * g->ingest_gbps, bound);
       if (rc != RT_OK) return rc;
       mx = bound[0];
     }
@@ -802,8 +891,8 @@ int rt_group_balance(rt_group* g, const float* header, int mode, int rounds, dou
     if (it + 1 < rounds) {
       rc = rt_calibrate_row_cost(cost.data(), H, b.data(), n, t.data());
       if (rc == RT_OK)
-        rc = gather ? rt_plan_strips_gather(cost.data(), H, n, W, g->link_gbps, g->ingest_gbps, b.data(), &root,
-                                            nullptr)
+        rc = gather ? rt_plan_strips_gather(cost.data(), H, n, W, bytes_scale * g->link_gbps,
+                                            bytes_scale * g->ingest_gbps, b.data(), &root, nullptr)
                     : rt_plan_strips(cost.data(), H, n, b.data());
       if (rc != RT_OK) return rc;
     }

@@ -3,7 +3,8 @@
 // (moving_light, main.cpp:541-551) or the rand buffer (fill_rand_buffer, main.cpp:535-539),
 // uploads the header, dispatches the mode's programs, advances the 8-slot ring
 // (main.cpp:619) and finally writes the last image as a PPM in place of the GL blit
-// (main.cpp:783-797, shader_fragment.glsl).
+// (main.cpp:783-797, shader_fragment.glsl): the 8-bit frame of rt_download_rgba8, or with --strips
+// of rt_group_download_rgba8, converted on the GPU (rt_present).
 //
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
 //               [--scene synthetic|1|5|6] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
@@ -30,18 +31,16 @@ static int check(int rc, const char* what) {
   return rc;
 }
 
-static void write_ppm(const char* path, const std::vector<float>& img, int W, int H) {
+// rgba: the 8-bit frame top row first (rt_download_rgba8 / rt_group_download_rgba8 with top_down),
+// converted on the GPU; the PPM drops the alpha byte
+static void write_ppm(const char* path, const std::vector<uint8_t>& rgba, int W, int H) {
   FILE* f = std::fopen(path, "wb");
   if (!f) return;
   std::fprintf(f, "P6\n%d %d\n255\n", W, H);
   std::vector<unsigned char> row(3 * (size_t)W);
-  for (int r = H - 1; r >= 0; --r) {  // GL texture origin is bottom-left
+  for (int r = 0; r < H; ++r) {
     for (int x = 0; x < W; ++x)
-      for (int c = 0; c < 3; ++c) {
-        float v = img[((size_t)r * W + x) * 4 + c];
-        v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-        row[3 * x + c] = (unsigned char)(v * 255.0f + 0.5f);
-      }
+      for (int c = 0; c < 3; ++c) row[3 * x + c] = rgba[((size_t)r * W + x) * 4 + c];
     std::fwrite(row.data(), 1, row.size(), f);
   }
   std::fclose(f);
@@ -78,6 +77,8 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   rt_group* g = nullptr;
   check(rt_group_create(strips, sd.data(), &cfg, nullptr, &g), "rt_group_create (peer access to the first device?)");
   if (pipeline) check(rt_group_enable_pipelining(g, 1), "rt_group_enable_pipelining");
+  // a frame that ends as a PPM is assembled as 8-bit strips (top row first), not float ones
+  if (!ppm.empty()) check(rt_group_enable_rgba8(g, 1, 1), "rt_group_enable_rgba8");
   std::vector<double> strip_ms(strips, 0.0);
   if (balance > 0) check(rt_group_balance(g, header.data(), mode, balance, strip_ms.data()), "rt_group_balance");
   std::vector<int> b(strips + 1);
@@ -94,8 +95,8 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   std::printf("%dx%d spp=%d mode=%d %d strips%s: %.3f ms/frame (wall), %.1f Mrays/s\n", W, H, A, mode, strips,
               pipeline ? " pipelined" : "", wall / frames, (double)W * H * (mode <= 2 ? A : 1) * frames / (wall * 1e3));
   if (!ppm.empty()) {
-    std::vector<float> img((size_t)W * H * 4);
-    check(rt_group_download_image(g, img.data()), "rt_group_download_image");
+    std::vector<uint8_t> img((size_t)W * H * 4);
+    check(rt_group_download_rgba8(g, img.data()), "rt_group_download_rgba8");
     write_ppm(ppm.c_str(), img, W, H);
   }
   rt_group_destroy(g);
@@ -161,8 +162,8 @@ int main(int argc, char** argv) {
               mode, pipeline ? " pipelined" : "", ms_frame, pipeline ? "wall" : "kernels",
               (double)W * H * (mode <= 2 ? A : 1) / (ms_frame * 1e3), wall);
   if (!ppm.empty()) {
-    std::vector<float> img((size_t)W * H * 4);
-    check(rt_download(ctx, nullptr, nullptr, nullptr, img.data()), "rt_download");
+    std::vector<uint8_t> img((size_t)W * H * 4);
+    check(rt_download_rgba8(ctx, 1, img.data()), "rt_download_rgba8");
     write_ppm(ppm.c_str(), img, W, H);
   }
   rt_destroy(ctx);

@@ -7,6 +7,7 @@
 //   rt_moving_light                 <- moving_light, src/main.cpp:541-551
 //   rt_init_scene                   <- init_scene1/5/6, src/scene.h:15-167
 //   rt_scenegen                     <- synthetic scenes of SURVEY.md §8d
+//   rt_quantize_rgba8               <- the blit into the 8-bit framebuffer, src/main.cpp:783-797
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -211,6 +212,29 @@ int rt_init_scene(float* header, int S, int AA, int which, float aspect) {
     return RT_E_INVAL;
   }
   return rt_fill_rand_buffer(header, S, AA, 7000);
+}
+
+// The blit's 8-bit conversion (src/main.cpp:783-797, shader_fragment.glsl:9-19), the rule
+// present_kernel (rt_kernels_impl.h) implements on the device: NaN and v <= 0 give 0, v >= 1 gives
+// 255, else v * 255 + 0.5 in binary32 (no contraction: this file is built with -ffp-contract=off)
+// truncated; alpha is 255.
+int rt_quantize_rgba8(const float* image, int width, int rows, int top_down, uint8_t* out) {
+  if (!image || !out || width <= 0 || rows <= 0) return RT_E_INVAL;
+  for (int j = 0; j < rows; ++j) {
+    const float* src = image + (size_t)(top_down ? rows - 1 - j : j) * width * 4;
+    uint8_t* dst = out + (size_t)j * width * 4;
+    for (int x = 0; x < width; ++x) {
+      for (int c = 0; c < 3; ++c) {
+        const float v = src[4 * x + c];
+        uint8_t q = 0;  // NaN fails both comparisons below
+        if (v >= 1.0f) q = 255;
+        else if (v > 0.0f) q = (uint8_t)(int)(v * 255.0f + 0.5f);
+        dst[4 * x + c] = q;
+      }
+      dst[4 * x + 3] = 255;
+    }
+  }
+  return RT_OK;
 }
 
 }  // extern "C"

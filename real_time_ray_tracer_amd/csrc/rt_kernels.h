@@ -169,6 +169,12 @@ struct GbufXfer {
 };
 hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream);
 
+// The blit into an 8-bit framebuffer (rt_present): `out` = [rows][W] RGBA8 (4-byte aligned) of
+// image = [rows][W] float4 by rt_quantize_rgba8's rule, output row j from image row j, or from row
+// rows - 1 - j when top_down.  Four pixels per lane and 16-byte stores when W % 4 == 0 and `out` is
+// 16-byte aligned, else one pixel per lane.
+hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream);
+
 // Device math self-test (rt_selftest_math).
 hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream);
 

@@ -2623,6 +2623,50 @@ hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// The blit into the 8-bit framebuffer (src/main.cpp:783-797, shader_fragment.glsl:9-19: colour
+// unchanged, alpha 1), rt_quantize_rgba8's rule on the device: NaN and v <= 0 give 0, v >= 1 gives
+// 255, else v * 255 + 0.5 in binary32 (two roundings, -ffp-contract=off) truncated; bytes r, g, b,
+// 255.  A streaming kernel: 16 B read and 4 B written per pixel, nothing reused.
+// As selects, not branches (twelve channels per lane would be twelve exec-mask regions): the value
+// converted is always in [0, 255.5), so the cast is defined for every input.
+__device__ __forceinline__ unsigned present_channel(float v) {
+  const float t = v * 255.0f + 0.5f;
+  const float inside = v > 0.0f ? t : 0.0f;  // NaN fails both comparisons: 0
+  return (unsigned)(v >= 1.0f ? 255.0f : inside);
+}
+__device__ __forceinline__ unsigned present_pixel(const float4 v) {
+  return present_channel(v.x) | (present_channel(v.y) << 8) | (present_channel(v.z) << 16) | 0xff000000u;
+}
+// Output row j is image row j, or row rows - 1 - j when top_down.  wide (W % 4 == 0 and `out` 16-byte
+// aligned, so every output row is): a lane takes four consecutive pixels of a row, four 16-byte
+// loads and one 16-byte store; else one pixel and one 4-byte store per lane (a dword store costs
+// several times a dwordx4 store's time per byte: the wide form is the one every frame size in use
+// takes).  Blocks of 256 lanes along a row, grid.y over the rows.
+__global__ __launch_bounds__(256) void present_kernel(const float4* __restrict__ image, unsigned* __restrict__ out,
+                                                      int W, int rows, int top_down, int wide) {
+  const int u = (int)(blockIdx.x * 256 + threadIdx.x);  // the lane's unit within a row
+  if (u >= (wide ? W >> 2 : W)) return;
+  for (int j = (int)blockIdx.y; j < rows; j += (int)gridDim.y) {
+    const float4* src = image + (size_t)(top_down ? rows - 1 - j : j) * W;
+    unsigned* dst = out + (size_t)j * W;
+    if (wide) {
+      const float4 a = src[4 * u], b = src[4 * u + 1], c = src[4 * u + 2], d = src[4 * u + 3];
+      *(uint4*)(dst + 4 * u) = make_uint4(present_pixel(a), present_pixel(b), present_pixel(c), present_pixel(d));
+    } else {
+      dst[u] = present_pixel(src[u]);
+    }
+  }
+}
+
+hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream) {
+  if (W <= 0 || rows <= 0) return hipSuccess;
+  const int wide = W % 4 == 0 && ((uintptr_t)out & 15) == 0;
+  const int units = wide ? W / 4 : W;
+  hipLaunchKernelGGL(present_kernel, dim3((unsigned)((units + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535)),
+                     dim3(256), 0, stream, image, (unsigned*)out, W, rows, top_down, wide);
+  return hipGetLastError();
+}
+
 // The production launch of `program` (rt_kernels.hip's launch_program; the A/B tools library
 // falls back to it): q = p with the derived table pointers and launch constants.
 inline FrameParams launch_params(const FrameParams& p) {

@@ -164,6 +164,10 @@ struct rt_ctx {
   float4* d_image_own = nullptr;
   float4* d_image = nullptr;
   hipStream_t img_stream = nullptr;  // the stream of the last launch that wrote the image
+  // rt_present: the image as [own_rows][W] RGBA8; the own buffer exists from the first present on
+  unsigned char* d_present_own = nullptr;
+  unsigned char* d_present_bound = nullptr;  // rt_bind_present (the caller's), else nullptr
+  unsigned char* d_present = nullptr;        // where the last present wrote (nullptr before the first)
   std::vector<float> header;   // host copy of the SSBO prefix
   std::vector<float4> table;   // host copy of the device table (rt::table_vec4 float4)
   bool have_header = false;
@@ -311,6 +315,7 @@ void free_all(rt_ctx* c) {
   for (auto p : c->nrm) if (p) (void)hipFree(p);
   for (auto p : c->dep) if (p) (void)hipFree(p);
   if (c->d_image_own) (void)hipFree(c->d_image_own);
+  if (c->d_present_own) (void)hipFree(c->d_present_own);
   for (int k = 0; k < kAoStreams; ++k) {
     if (c->d_shapes_buf[k]) (void)hipFree(c->d_shapes_buf[k]);
   }
@@ -1646,6 +1651,53 @@ void* rt_image_device_ptr(rt_ctx* c) { return c ? (void*)c->d_image : nullptr; }
 int rt_bind_image(rt_ctx* c, void* p) {
   if (!c) return RT_E_INVAL;
   c->d_image = p ? (float4*)p : c->d_image_own;
+  return RT_OK;
+}
+
+// ---- the blit (src/main.cpp:783-797) ----------------------------------------------------
+int rt_present(rt_ctx* c, int top_down) {
+  if (!c) return RT_E_INVAL;
+  RT_HIP(c, hipSetDevice(c->device));
+  // on the stream of the last launch that wrote the image: the conversion reads the image after
+  // that launch, and the next image writer is ordered after this stream's work (rt_image_stream)
+  hipStream_t st = (hipStream_t)rt_image_stream(c);
+  const size_t bytes = (size_t)c->own_rows * c->cfg.width * 4;
+  unsigned char* dst = c->d_present_bound;
+  if (!dst) {
+    if (!c->d_present_own) {
+      hipError_t e = hipMalloc(&c->d_present_own, bytes);
+      if (e == hipErrorOutOfMemory) {
+        c->last_hip = (int)e;
+        c->d_present_own = nullptr;
+        return RT_E_NOMEM;
+      }
+      RT_HIP(c, e);
+      RT_HIP(c, hipMemsetAsync(c->d_present_own, 0, bytes, st));
+    }
+    dst = c->d_present_own;
+  }
+  RT_HIP(c, rt::launch_present(c->d_image, dst, c->cfg.width, c->own_rows, top_down != 0, st));
+  c->d_present = dst;
+  return RT_OK;
+}
+
+void* rt_present_device_ptr(rt_ctx* c) { return c ? (void*)c->d_present : nullptr; }
+
+int rt_bind_present(rt_ctx* c, void* p) {
+  if (!c || ((uintptr_t)p & 3)) return RT_E_INVAL;  // the kernel stores whole pixels
+  c->d_present_bound = (unsigned char*)p;
+  return RT_OK;
+}
+
+int rt_download_rgba8(rt_ctx* c, int top_down, uint8_t* out) {
+  if (!c || !out) return RT_E_INVAL;
+  RT_HIP(c, hipSetDevice(c->device));
+  int rc = rt_present(c, top_down);
+  if (rc == RT_OK) rc = join(c);
+  if (rc == RT_OK) rc = sync_all(c);
+  if (rc != RT_OK) return rc;
+  RT_HIP(c, hipMemcpyAsync(out, c->d_present, (size_t)c->own_rows * c->cfg.width * 4, hipMemcpyDeviceToHost, c->stream));
+  RT_HIP(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 

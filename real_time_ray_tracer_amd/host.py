@@ -319,6 +319,29 @@ class Renderer:
         self._c(self._lib.rt_bind_image(self.ctx, C.c_void_p(device_ptr) if device_ptr else None),
                 "rt_bind_image")
 
+    # 8-bit display output (the blit, src/main.cpp:783-797)
+    def present(self, top_down: bool = True):
+        """Enqueue the conversion of the current image to RGBA8 (rt_present) behind the launch that
+        wrote it; returns without waiting.  top_down: output row 0 is the image's top row."""
+        self._c(self._lib.rt_present(self.ctx, int(bool(top_down))), "rt_present")
+
+    def image8(self, top_down: bool = True) -> np.ndarray:
+        """present + wait + copy (rt_download_rgba8): uint8 [R][W][4], equal to
+        quantize_rgba8(self.image(), top_down)."""
+        out = np.empty((self.R, self.W, 4), np.uint8)
+        self._c(self._lib.rt_download_rgba8(self.ctx, int(bool(top_down)), out.ctypes.data_as(C.c_void_p)),
+                "rt_download_rgba8")
+        return out
+
+    def present_device_ptr(self) -> int:
+        """Where the last present wrote ([R][W] RGBA8 on the device); 0 before the first present."""
+        return self._lib.rt_present_device_ptr(self.ctx) or 0
+
+    def bind_present(self, device_ptr: int | None):
+        """Later presents write into a caller-owned device buffer of R*W*4 bytes (None: the context's own)."""
+        self._c(self._lib.rt_bind_present(self.ctx, C.c_void_p(device_ptr) if device_ptr else None),
+                "rt_bind_present")
+
     # host-buffer parity path (the reference's call shape)
     def compute_one_shader(self, ssbo: SSBO, frame_num: int, program: int, image: np.ndarray | None = None) -> int:
         return self._c(self._lib.rt_compute_one_shader(self.ctx, ssbo.data.ctypes.data_as(C.c_void_p), frame_num,
@@ -500,12 +523,40 @@ class StripGroup:
         self._c(self._lib.rt_group_download_image(self.g, fptr(im)), "rt_group_download_image")
         return im
 
+    def enable_rgba8(self, on: bool = True, top_down: bool = True):
+        """8-bit output (rt_group_enable_rgba8): every strip's frame is followed by its present and the
+        strips are assembled as an [H][W] RGBA8 frame, a quarter of the float strips' bytes; image()
+        raises while it is on."""
+        self._c(self._lib.rt_group_enable_rgba8(self.g, int(bool(on)), int(bool(top_down))), "rt_group_enable_rgba8")
+
+    def image8(self) -> np.ndarray:
+        """The assembled 8-bit frame, uint8 [H][W][4], in the row order given to enable_rgba8."""
+        out = np.empty((self.H, self.W, 4), np.uint8)
+        self._c(self._lib.rt_group_download_rgba8(self.g, out.ctypes.data_as(C.c_void_p)), "rt_group_download_rgba8")
+        return out
+
+    def rgba8_device_ptr(self) -> int:
+        return self._lib.rt_group_rgba8_device_ptr(self.g) or 0
+
     def balance(self, header: Header, mode: int, rounds: int = 3) -> list[float]:
         """Cost-balance the strips (probe frame + `rounds` timed plans); returns the kept plan's
         per-strip ms per frame.  The strips restart with fresh rings."""
         ms = (C.c_double * self.n)()
         self._c(self._lib.rt_group_balance(self.g, header._p(), mode, rounds, ms), "rt_group_balance")
         return list(ms)
+
+
+def quantize_rgba8(image, top_down: bool = True) -> np.ndarray:
+    """rt_quantize_rgba8 (host only): float32 [R][W][4] -> uint8 [R][W][4] by the blit's rule (NaN and
+    v <= 0 -> 0, v >= 1 -> 255, else float32 v * 255 + 0.5 truncated; alpha 255), the specification
+    of Renderer.present.  top_down: output row j is image row R - 1 - j."""
+    im = np.ascontiguousarray(image, np.float32)
+    if im.ndim != 3 or im.shape[2] != 4:
+        raise ValueError(f"quantize_rgba8: need an [R][W][4] image, got shape {im.shape}")
+    out = np.empty(im.shape, np.uint8)
+    _check(_lib.load().rt_quantize_rgba8(fptr(im), im.shape[1], im.shape[0], int(bool(top_down)),
+                                         out.ctypes.data_as(C.c_void_p)), "rt_quantize_rgba8")
+    return out
 
 
 def plan_strips(row_cost, n: int) -> list[int]:
