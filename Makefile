@@ -41,7 +41,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
 $(OBJDIR)/rt_host.o: $(CSRC)/rt_host.cpp include/rt/*.h | $(OBJDIR)
 	$(HIPCC) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -c $< -o $@
 
-$(OBJDIR)/rt_group.o: $(CSRC)/rt_group.cpp include/rt/*.h | $(OBJDIR)
+$(OBJDIR)/rt_group.o: $(CSRC)/rt_group.cpp $(CSRC)/rt_kernels.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Iinclude -c $< -o $@
 
 # BUILD_INFO: sha1 of the library's sources (+ the git commit they were built at, "+dirty" if

@@ -22,7 +22,8 @@
  *   - all GPU work is ordered on the context's HIP stream (rt_set_stream to share one).
  *
  * Host-only helpers (rt_pack_*, rt_camera_basis, rt_fill_rand_buffer, rt_moving_light,
- * rt_scenegen, rt_init_scene, rt_quantize_rgba8, rt_strerror, rt_version) never touch the GPU.
+ * rt_scenegen, rt_init_scene, rt_quantize_rgba8, rt_resample_rgba8, rt_strerror, rt_version) never
+ * touch the GPU.
  */
 #ifndef RT_ABI_H
 #define RT_ABI_H
@@ -226,6 +227,56 @@ int rt_download_rgba8(rt_ctx* ctx, int top_down, uint8_t* out);
  * specification of rt_present in C; never touches the GPU. */
 int rt_quantize_rgba8(const float* image, int width, int rows, int top_down, uint8_t* out);
 
+/* ---- 8-bit display output at window size (the blit's scaling, src/main.cpp:381-388, 783-797) -- */
+/* The reference draws the image as a textured quad into whatever framebuffer the window has
+ * (glViewport every frame, src/main.cpp:783-797; the resize callback, 298-305), the texture sampled
+ * with GL_LINEAR for both filters and GL_CLAMP_TO_EDGE (381-388): its screenshots are a 440x330
+ * render in a 1920x1080 window.  These entry points are that blit for any output size, in either
+ * direction; scaling down is plain bilinear with no mip chain, like GL_LINEAR minification.
+ * The rule.  Source image = [R][W] rgba32f (row 0 = bottom row), output = [out_h][out_w] RGBA8, all
+ * four sizes in [1, RT_PRESENT_SCALED_MAX].  For output column i, in 32-bit integers:
+ *   n = (2*i + 1)*W - out_w, d = 2*out_w, x0 = floor(n / d), rem = n - x0*d  (0 <= rem < d),
+ *   a = (float)rem / (float)d  (one correctly rounded binary32 division of two exact operands),
+ *   taps = columns clamp(x0, 0, W-1) and clamp(x0 + 1, 0, W-1): clamping moves the index only, the
+ *   weight stays as computed.
+ * Rows likewise from R, out_h and output row j (counted from the bottom): y0, y1, b.  Per channel
+ * of r, g, b in binary32 without contraction, in this order: on each of the two source rows
+ *   h = (a == 0) ? t0 : ((1.0f - a)*t0 + a*t1),   then   v = (b == 0) ? h0 : ((1.0f - b)*h0 + b*h1),
+ * then v is converted by rt_quantize_rgba8's rule; alpha 255; bytes r, g, b, a.  The selects on a
+ * zero weight are part of the rule: at out_w == W and out_h == R every weight is 0 and the result
+ * is exactly rt_present's, and a NaN or infinity under a zero weight does not reach a result.
+ * top_down != 0 reverses the output rows (output row j = the bottom-up result's row out_h - 1 - j).
+ * Whole-frame contexts only: the filter reads rows a strip context (rows a proper subset of the
+ * frame) does not hold, so every call below returns RT_E_STATE (the pointer query NULL) for one.
+ * All opt-in: a context that never calls these allocates nothing and launches nothing. */
+#define RT_PRESENT_SCALED_MAX 16384
+/* Enqueue the scaled blit of the current image (the context's own or rt_bind_image's) on
+ * rt_image_stream(ctx), exactly where rt_present enqueues: it reads the image after the launch
+ * that wrote it and the next image writer is ordered after it.  It creates no stream and no event
+ * and returns without waiting.  It writes into the buffer given to rt_bind_present_scaled, else
+ * into a buffer of the context's own, allocated (and zeroed) by the first scaled present that
+ * needs it and kept for every size that fits.  A larger size (a window resize) replaces the own
+ * buffer: before the old one is freed the call waits for all of the context's streams, as
+ * rt_synchronize does; every scaled present was enqueued on one of them, so none still writes it.
+ * rt_present's buffer and rt_bind_present are not touched. */
+int rt_present_scaled(rt_ctx* ctx, int out_width, int out_height, int top_down);
+/* Where the last rt_present_scaled wrote ([out_height][out_width] RGBA8 on the device); NULL before
+ * the first. */
+void* rt_present_scaled_device_ptr(rt_ctx* ctx);
+/* The size of the last rt_present_scaled (RT_E_STATE before the first).  Either pointer may be NULL. */
+int rt_present_scaled_size(rt_ctx* ctx, int* out_width, int* out_height);
+/* Later scaled presents write into a caller-owned device buffer, 4-byte aligned (16-byte aligned for
+ * the 16-byte stores), of at least out_width*out_height*4 bytes for every size the caller presents
+ * at; NULL = the context's own buffer.  Does not wait for anything. */
+int rt_bind_present_scaled(rt_ctx* ctx, void* device_ptr);
+/* rt_present_scaled, wait (as rt_download_rgba8 does), copy out_width*out_height*4 bytes to `out`. */
+int rt_download_rgba8_scaled(rt_ctx* ctx, int out_width, int out_height, int top_down, uint8_t* out);
+/* Host-only: the rule above on image = [rows][width] rgba32f into out = [out_rows][out_width][4].
+ * The specification of rt_present_scaled in C; never touches the GPU.  RT_E_INVAL for a NULL
+ * pointer or a size outside [1, RT_PRESENT_SCALED_MAX]. */
+int rt_resample_rgba8(const float* image, int width, int rows, int out_width, int out_rows, int top_down,
+                      uint8_t* out);
+
 /* ---- host-buffer parity path (mirrors the reference call shape) -------------------- */
 /* compute_one_shader(frame_num, prog) (src/main.cpp:580-620): sets mode.y = frame_num in
  * `ssbo` (a whole ssbo_data-layout host buffer of rt_ssbo_bytes(S,spp,W,R,F) bytes), copies
@@ -336,6 +387,12 @@ int rt_group_enable_rgba8(rt_group* g, int on, int top_down);
 int rt_group_download_rgba8(rt_group* g, uint8_t* out);
 /* The 8-bit frame on devices[0]; NULL while 8-bit output is off. */
 void* rt_group_rgba8_device_ptr(rt_group* g);
+/* The assembled float frame at window size, on demand (the rule of rt_present_scaled): waits for the
+ * frames in flight (rt_group_synchronize), runs the scaled blit once on devices[0] over the [H][W]
+ * frame and copies out_width*out_height*4 bytes to `out`.  Its device scratch is allocated by the
+ * first call, regrown by a larger size and freed by rt_group_destroy.  RT_E_STATE while 8-bit
+ * output is on (the float frame is not assembled then). */
+int rt_group_download_rgba8_scaled(rt_group* g, int out_width, int out_height, int top_down, uint8_t* out);
 /* Rescale row_cost so every strip's total equals its measured time (row shape kept). */
 int rt_calibrate_row_cost(double* row_cost, int H, const int* bounds, int n, const double* strip_ms);
 

@@ -76,6 +76,13 @@ SIGNATURES = {
     "rt_bind_present": (C.c_int, [_ctx, _vp]),
     "rt_download_rgba8": (C.c_int, [_ctx, C.c_int, _vp]),
     "rt_quantize_rgba8": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _vp]),
+    "rt_present_scaled": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
+    "rt_present_scaled_device_ptr": (_vp, [_ctx]),
+    "rt_present_scaled_size": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rt_bind_present_scaled": (C.c_int, [_ctx, _vp]),
+    "rt_download_rgba8_scaled": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _vp]),
+    "rt_resample_rgba8": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "rt_group_download_rgba8_scaled": (C.c_int, [_grp, C.c_int, C.c_int, C.c_int, _vp]),
     "rt_group_enable_rgba8": (C.c_int, [_grp, C.c_int, C.c_int]),
     "rt_group_download_rgba8": (C.c_int, [_grp, _vp]),
     "rt_group_rgba8_device_ptr": (_vp, [_grp]),

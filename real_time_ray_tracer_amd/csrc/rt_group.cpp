@@ -14,7 +14,8 @@
 //     after everything on that stream, the copy included.
 // With 8-bit output on (rt_group_enable_rgba8) every strip's frame is followed by rt_present, the
 // blit's conversion, and what is assembled is an [H][W] RGBA8 frame: the same two paths with a
-// quarter of the bytes on the links (finish_strip).
+// quarter of the bytes on the links (finish_strip).  The float frame at a window's size, the blit's
+// bilinear scaling, is made on demand from the assembled frame (rt_group_download_rgba8_scaled).
 // Each strip keeps its own g-buffer ring for its rows plus a 1-row halo (rt_create), so no
 // strip reads another's data: the copies into the frame are the only transfers.
 // One host thread per strip enqueues its strip's work, so the per-frame host cost does not add
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "../../include/rt/abi.h"
+#include "rt_kernels.h"
 
 namespace {
 
@@ -131,6 +133,9 @@ struct rt_group {
   bool rgba8 = false;
   bool top_down = false;
   unsigned char* frame8 = nullptr;  // [H][W][4] on devices[0] while rgba8
+  // rt_group_download_rgba8_scaled: the frame at window size on devices[0], from the first call on
+  unsigned char* scaled = nullptr;
+  size_t scaled_bytes = 0;
 };
 
 namespace {
@@ -543,6 +548,10 @@ int rt_group_destroy(rt_group* g) {
     (void)hipSetDevice(g->devices[0]);
     (void)hipFree(g->frame8);
   }
+  if (g->scaled) {
+    (void)hipSetDevice(g->devices[0]);
+    (void)hipFree(g->scaled);
+  }
   delete g;
   return RT_OK;
 }
@@ -717,6 +726,38 @@ int rt_group_download_rgba8(rt_group* g, uint8_t* out) {
 }
 
 void* rt_group_rgba8_device_ptr(rt_group* g) { return g && g->rgba8 ? (void*)g->frame8 : nullptr; }
+
+// The blit at window size over the assembled float frame (src/main.cpp:381-388, 783-797), on demand:
+// once the frames in flight are finished the frame on devices[0] is complete, so one launch on the
+// device's NULL stream converts it and the (blocking) copy that follows waits for the launch.  The
+// scratch is idle whenever this returns, so a larger size may free it at once.
+int rt_group_download_rgba8_scaled(rt_group* g, int out_width, int out_height, int top_down, uint8_t* out) {
+  if (!g || !out || out_width < 1 || out_height < 1 || out_width > RT_PRESENT_SCALED_MAX ||
+      out_height > RT_PRESENT_SCALED_MAX)
+    return RT_E_INVAL;
+  if (g->rgba8) return RT_E_STATE;  // the float frame is not assembled while 8-bit output is on
+  int rc = rt_group_synchronize(g);
+  if (rc != RT_OK) return rc;
+  const size_t bytes = (size_t)out_width * out_height * 4;
+  hipError_t e = hipSetDevice(g->devices[0]);
+  if (e == hipSuccess && g->scaled_bytes < bytes) {
+    if (g->scaled) e = hipFree(g->scaled);
+    g->scaled = nullptr;
+    g->scaled_bytes = 0;
+    if (e == hipSuccess) e = hipMalloc(&g->scaled, bytes);
+    if (e == hipSuccess) g->scaled_bytes = bytes;
+    else g->scaled = nullptr;
+  }
+  if (e == hipSuccess)
+    e = rt::launch_present_scaled(g->frame, g->cfg.width, g->cfg.height, g->scaled, out_width, out_height,
+                                  top_down != 0, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, g->scaled, bytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    g->last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_HIP;
+  }
+  return RT_OK;
+}
 
 int rt_group_download_image(rt_group* g, float* image) {
   if (!g || !image) return RT_E_INVAL;

@@ -4,11 +4,13 @@
 // uploads the header, dispatches the mode's programs, advances the 8-slot ring
 // (main.cpp:619) and finally writes the last image as a PPM in place of the GL blit
 // (main.cpp:783-797, shader_fragment.glsl): the 8-bit frame of rt_download_rgba8, or with --strips
-// of rt_group_download_rgba8, converted on the GPU (rt_present).
+// of rt_group_download_rgba8, converted on the GPU (rt_present).  With --ppm-size WxH the PPM has that
+// size instead, the frame scaled as the reference's blit scales it into its window (GL_LINEAR,
+// main.cpp:381-388), on the GPU as well: rt_download_rgba8_scaled / rt_group_download_rgba8_scaled.
 //
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
 //               [--scene synthetic|1|5|6] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
-//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS]
+//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH]
 // --strips G > 1 renders the frame as G row strips through the rt_group_* entry points: strip i
 // on device devices[i % #devices] (default, without --devices: every visible device in turn,
 // starting at --device), cost-balanced with --balance ROUNDS timed plans (0: equal strips),
@@ -48,7 +50,8 @@ static void write_ppm(const char* path, const std::vector<uint8_t>& rgba, int W,
 
 // The frame as `strips` row strips over the devices in `devlist` (rt_group_*).
 static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode, int frames, int pipeline,
-                      int strips, const std::string& devlist, int device, int balance, const std::string& ppm) {
+                      int strips, const std::string& devlist, int device, int balance, const std::string& ppm,
+                      int ppm_w, int ppm_h) {
   std::vector<int> devs;
   for (size_t p = 0; p < devlist.size();) {
     size_t q = devlist.find(',', p);
@@ -77,8 +80,9 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   rt_group* g = nullptr;
   check(rt_group_create(strips, sd.data(), &cfg, nullptr, &g), "rt_group_create (peer access to the first device?)");
   if (pipeline) check(rt_group_enable_pipelining(g, 1), "rt_group_enable_pipelining");
-  // a frame that ends as a PPM is assembled as 8-bit strips (top row first), not float ones
-  if (!ppm.empty()) check(rt_group_enable_rgba8(g, 1, 1), "rt_group_enable_rgba8");
+  // a frame that ends as a PPM is assembled as 8-bit strips (top row first), not float ones; one
+  // scaled to --ppm-size is filtered from the float frame, which 8-bit strips would not assemble
+  if (!ppm.empty() && ppm_w == 0) check(rt_group_enable_rgba8(g, 1, 1), "rt_group_enable_rgba8");
   std::vector<double> strip_ms(strips, 0.0);
   if (balance > 0) check(rt_group_balance(g, header.data(), mode, balance, strip_ms.data()), "rt_group_balance");
   std::vector<int> b(strips + 1);
@@ -94,7 +98,11 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   const int W = cfg.width, H = cfg.height, A = cfg.spp;
   std::printf("%dx%d spp=%d mode=%d %d strips%s: %.3f ms/frame (wall), %.1f Mrays/s\n", W, H, A, mode, strips,
               pipeline ? " pipelined" : "", wall / frames, (double)W * H * (mode <= 2 ? A : 1) * frames / (wall * 1e3));
-  if (!ppm.empty()) {
+  if (!ppm.empty() && ppm_w > 0) {
+    std::vector<uint8_t> img((size_t)ppm_w * ppm_h * 4);
+    check(rt_group_download_rgba8_scaled(g, ppm_w, ppm_h, 1, img.data()), "rt_group_download_rgba8_scaled");
+    write_ppm(ppm.c_str(), img, ppm_w, ppm_h);
+  } else if (!ppm.empty()) {
     std::vector<uint8_t> img((size_t)W * H * 4);
     check(rt_group_download_rgba8(g, img.data()), "rt_group_download_rgba8");
     write_ppm(ppm.c_str(), img, W, H);
@@ -105,6 +113,7 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
 
 int main(int argc, char** argv) {
   int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0;
+  int ppm_w = 0, ppm_h = 0;  // --ppm-size (0: the frame's own size)
   std::string scene = "1", ppm, devlist;
   unsigned long long seed = 1234;
   for (int i = 1; i + 1 < argc; i += 2) {
@@ -123,6 +132,13 @@ int main(int argc, char** argv) {
     else if (k == "--strips") strips = std::atoi(v.c_str());
     else if (k == "--devices") devlist = v;
     else if (k == "--balance") balance = std::atoi(v.c_str());
+    else if (k == "--ppm-size") {
+      if (std::sscanf(v.c_str(), "%dx%d", &ppm_w, &ppm_h) != 2 || ppm_w < 1 || ppm_h < 1 ||
+          ppm_w > RT_PRESENT_SCALED_MAX || ppm_h > RT_PRESENT_SCALED_MAX) {
+        std::fprintf(stderr, "rt_headless: --ppm-size wants WxH with both in [1, %d]\n", RT_PRESENT_SCALED_MAX);
+        return 2;
+      }
+    }
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   const float aspect = (W * 3 == H * 4) ? 1.333333f : 1.777777f;  // main.cpp:39-40
@@ -132,7 +148,8 @@ int main(int argc, char** argv) {
   else check(rt_init_scene(header.data(), S, A, std::atoi(scene.c_str()), aspect), "rt_init_scene");
 
   rt_config cfg{W, H, S, A, RT_NUM_FRAMES, RT_RECURSION_DEPTH, 0, 0};
-  if (strips > 1) return run_strips(cfg, header, mode, frames, pipeline, strips, devlist, device, balance, ppm);
+  if (strips > 1) return run_strips(cfg, header, mode, frames, pipeline, strips, devlist, device, balance, ppm,
+                                ppm_w, ppm_h);
   rt_ctx* ctx = nullptr;
   check(rt_create(device, &cfg, &ctx), "rt_create");
   check(rt_enable_timing(ctx, 1), "rt_enable_timing");
@@ -161,7 +178,11 @@ int main(int argc, char** argv) {
   std::printf("%dx%d spp=%d objects=%d mode=%d%s: %.3f ms/frame (%s), %.1f Mrays/s, wall %.1f ms\n", W, H, A, N,
               mode, pipeline ? " pipelined" : "", ms_frame, pipeline ? "wall" : "kernels",
               (double)W * H * (mode <= 2 ? A : 1) / (ms_frame * 1e3), wall);
-  if (!ppm.empty()) {
+  if (!ppm.empty() && ppm_w > 0) {
+    std::vector<uint8_t> img((size_t)ppm_w * ppm_h * 4);
+    check(rt_download_rgba8_scaled(ctx, ppm_w, ppm_h, 1, img.data()), "rt_download_rgba8_scaled");
+    write_ppm(ppm.c_str(), img, ppm_w, ppm_h);
+  } else if (!ppm.empty()) {
     std::vector<uint8_t> img((size_t)W * H * 4);
     check(rt_download_rgba8(ctx, 1, img.data()), "rt_download_rgba8");
     write_ppm(ppm.c_str(), img, W, H);

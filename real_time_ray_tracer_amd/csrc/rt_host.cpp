@@ -8,9 +8,11 @@
 //   rt_init_scene                   <- init_scene1/5/6, src/scene.h:15-167
 //   rt_scenegen                     <- synthetic scenes of SURVEY.md §8d
 //   rt_quantize_rgba8               <- the blit into the 8-bit framebuffer, src/main.cpp:783-797
+//   rt_resample_rgba8               <- the same blit into a window of another size (GL_LINEAR, 381-388)
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "../../include/rt/abi.h"
 
@@ -232,6 +234,69 @@ int rt_quantize_rgba8(const float* image, int width, int rows, int top_down, uin
         dst[4 * x + c] = q;
       }
       dst[4 * x + 3] = 255;
+    }
+  }
+  return RT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One axis of the blit's GL_LINEAR sampling (src/main.cpp:381-388, 783-797): output sample i of
+// `dst` over `src` texels sits at texel coordinate (2i + 1) * src / (2 * dst) - 1/2 = n / d - 1 in
+// integers; i0 is its floor, w the fraction (one correctly rounded binary32 division of two exact
+// operands, rem < d <= 2^15).  GL_CLAMP_TO_EDGE moves the tap indices only, never the weight.
+struct ScaleTap {
+  int i0, i1;
+  float w;
+};
+ScaleTap scale_tap(int i, int src, int dst) {
+  const int n = (2 * i + 1) * src - dst, d = 2 * dst;      // n + d > 0; all below 2^30
+  const int x0 = (int)((unsigned)(n + d) / (unsigned)d) - 1;  // floor(n / d)
+  const int rem = n - x0 * d;                              // 0 <= rem < d
+  const int hi = src - 1;
+  return ScaleTap{x0 < 0 ? 0 : (x0 > hi ? hi : x0), x0 + 1 < 0 ? 0 : (x0 + 1 > hi ? hi : x0 + 1),
+                  (float)rem / (float)d};
+}
+// the select on a zero weight is part of the rule: that tap's texel (NaN, inf) does not reach the result
+inline float scale_mix(float w, float t0, float t1) { return w == 0.0f ? t0 : ((1.0f - w) * t0 + w * t1); }
+
+inline uint8_t quantize_channel(float v) {  // rt_quantize_rgba8's rule
+  if (v >= 1.0f) return 255;
+  if (v > 0.0f) return (uint8_t)(int)(v * 255.0f + 0.5f);
+  return 0;  // NaN fails both comparisons
+}
+
+}  // namespace
+
+extern "C" {
+
+// The blit at window size (src/main.cpp:783-797 with the texture's GL_LINEAR / GL_CLAMP_TO_EDGE,
+// 381-388), the rule present_scaled_kernel (rt_kernels_impl.h) implements on the device: per output
+// pixel the two taps and the weight of each axis (scale_tap), per channel the blend along x on both
+// source rows, then along y, in binary32 without contraction, then rt_quantize_rgba8's conversion.
+int rt_resample_rgba8(const float* image, int width, int rows, int out_width, int out_rows, int top_down,
+                      uint8_t* out) {
+  const int lim = RT_PRESENT_SCALED_MAX;
+  if (!image || !out || width < 1 || rows < 1 || out_width < 1 || out_rows < 1 || width > lim || rows > lim ||
+      out_width > lim || out_rows > lim)
+    return RT_E_INVAL;
+  std::vector<ScaleTap> tx((size_t)out_width);
+  for (int i = 0; i < out_width; ++i) tx[i] = scale_tap(i, width, out_width);
+  for (int j = 0; j < out_rows; ++j) {
+    const ScaleTap ty = scale_tap(top_down ? out_rows - 1 - j : j, rows, out_rows);
+    const float* r0 = image + (size_t)ty.i0 * width * 4;
+    const float* r1 = image + (size_t)ty.i1 * width * 4;
+    uint8_t* dst = out + (size_t)j * out_width * 4;
+    for (int i = 0; i < out_width; ++i) {
+      const size_t a0 = (size_t)tx[i].i0 * 4, a1 = (size_t)tx[i].i1 * 4;
+      for (int c = 0; c < 3; ++c) {
+        const float h0 = scale_mix(tx[i].w, r0[a0 + c], r0[a1 + c]);
+        const float h1 = scale_mix(tx[i].w, r1[a0 + c], r1[a1 + c]);
+        dst[4 * i + c] = quantize_channel(scale_mix(ty.w, h0, h1));
+      }
+      dst[4 * i + 3] = 255;
     }
   }
   return RT_OK;

@@ -175,6 +175,14 @@ hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream);
 // 16-byte aligned, else one pixel per lane.
 hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream);
 
+// The blit at window size (rt_present_scaled): `out` = [out_h][out_w] RGBA8 (4-byte aligned) of
+// image = [R][W] float4 sampled bilinearly with clamped edges, by rt_resample_rgba8's rule; output
+// row j counts from the bottom, or from the top when top_down.  All four sizes in [1, 16384]
+// (hipErrorInvalidValue otherwise).  Four pixels per lane and 16-byte stores when out_w % 4 == 0 and
+// `out` is 16-byte aligned, else one pixel per lane.
+hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, int out_w, int out_h, int top_down,
+                                 hipStream_t stream);
+
 // Device math self-test (rt_selftest_math).
 hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream);
 

@@ -2667,6 +2667,103 @@ hipError_t launch_present(const float4* image, void* out, int W, int rows, int t
   return hipGetLastError();
 }
 
+// The blit at window size (rt_present_scaled; the rule is stated in include/rt/abi.h and specified
+// by rt_resample_rgba8, rt_host.cpp): the image sampled as the reference's texture is, GL_LINEAR
+// with GL_CLAMP_TO_EDGE (src/main.cpp:381-388), then present_channel's conversion.
+// One axis: output sample i of `dst` over `src` texels -> the two clamped taps and the weight of
+// the second.  n + d > 0, so floor(n / d) is one unsigned division; rem and d are exact in
+// binary32 (< 2^16) and the build's '/' is the IEEE division (RT_MATH_DIV).
+struct ScaleTap {
+  int i0, i1;
+  float w;
+};
+__device__ __forceinline__ ScaleTap scale_tap(int i, int src, int dst) {
+  const int n = (2 * i + 1) * src - dst, d = 2 * dst;
+  const int x0 = (int)((unsigned)(n + d) / (unsigned)d) - 1;
+  const int rem = n - x0 * d;
+  return ScaleTap{min(max(x0, 0), src - 1), min(max(x0 + 1, 0), src - 1), (float)rem / (float)d};
+}
+// (w == 0) ? t0 : (1 - w) * t0 + w * t1 as a select: a zero-weight tap (NaN, inf) never reaches the
+// result, and at equal sizes the blit is present_kernel's bit for bit.  u = 1.0f - w, hoisted.
+__device__ __forceinline__ float scale_mix(float w, float u, float t0, float t1) {
+  const float m = u * t0 + w * t1;
+  return w == 0.0f ? t0 : m;
+}
+__device__ __forceinline__ unsigned scaled_channel(float a, float ua, float b, float ub, float t00, float t01,
+                                                   float t10, float t11) {
+  return present_channel(scale_mix(b, ub, scale_mix(a, ua, t00, t01), scale_mix(a, ua, t10, t11)));
+}
+// A lane's N consecutive output pixels of every row it walks.  The column taps are computed once,
+// before the row loop (one integer and one float division per column); a row's taps depend on the
+// row index alone, so they are wave-uniform.  Per pixel four 16-byte taps at clamped indices:
+// nothing outside [R][W] is read.  tx[] is indexed by unrolled constants only (registers).
+template <int N>
+__device__ __forceinline__ void present_scaled_rows(const float4* __restrict__ image, int W, int R,
+                                                    unsigned* __restrict__ out, int out_w, int out_h, int top_down,
+                                                    int u) {
+  ScaleTap tx[N];
+  float ux[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    tx[k] = scale_tap(N * u + k, W, out_w);
+    ux[k] = 1.0f - tx[k].w;
+  }
+  for (int j = (int)blockIdx.y; j < out_h; j += (int)gridDim.y) {
+    const ScaleTap ty = scale_tap(top_down ? out_h - 1 - j : j, R, out_h);
+    const float uy = 1.0f - ty.w;
+    const float4* r0 = image + (size_t)ty.i0 * W;
+    const float4* r1 = image + (size_t)ty.i1 * W;
+    unsigned px[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const float4 p00 = r0[tx[k].i0], p01 = r0[tx[k].i1], p10 = r1[tx[k].i0], p11 = r1[tx[k].i1];
+      const float a = tx[k].w, ua = ux[k];
+      px[k] = scaled_channel(a, ua, ty.w, uy, p00.x, p01.x, p10.x, p11.x) |
+              (scaled_channel(a, ua, ty.w, uy, p00.y, p01.y, p10.y, p11.y) << 8) |
+              (scaled_channel(a, ua, ty.w, uy, p00.z, p01.z, p10.z, p11.z) << 16) | 0xff000000u;
+    }
+    unsigned* dst = out + (size_t)j * out_w + N * u;
+    if constexpr (N == 4) *(uint4*)dst = make_uint4(px[0], px[1], px[2], px[3]);
+    else *dst = px[0];
+  }
+}
+// present_kernel's outline: wide (out_w % 4 == 0 and `out` 16-byte aligned) a lane owns four
+// consecutive output pixels of a row and writes one 16-byte store, else one pixel and one 4-byte
+// store.  Blocks of 256 lanes along the output row, grid.y striding over the output rows.
+__global__ __launch_bounds__(256) void present_scaled_kernel(const float4* __restrict__ image, int W, int R,
+                                                             unsigned* __restrict__ out, int out_w, int out_h,
+                                                             int top_down, int wide) {
+  const int u = (int)(blockIdx.x * 256 + threadIdx.x);  // the lane's unit within an output row
+  if (u >= (wide ? out_w >> 2 : out_w)) return;
+  if (wide) present_scaled_rows<4>(image, W, R, out, out_w, out_h, top_down, u);
+  else present_scaled_rows<1>(image, W, R, out, out_w, out_h, top_down, u);
+}
+
+// grid.y: about kScaledBlocks workgroups in all, two per CU, so at display sizes a lane walks
+// several rows and its column taps are computed once for all of them; never more rows of blocks
+// than output rows.  Measured at 512 / 1024 / 2048 / 4096 (DESIGN.md §5 "Round 12"): more
+// workgroups never helped (the kernel waits on its loads' cache lines, not on occupancy), and 512
+// is the fastest at 3840x2160 -> 1920x1080 (0.027 against 0.034 ms at 1024).
+#ifndef RT_SCALED_BLOCKS
+#define RT_SCALED_BLOCKS 512  // (A/B builds override it)
+#endif
+constexpr int kScaledBlocks = RT_SCALED_BLOCKS;
+constexpr int kScaledMax = 16384;  // RT_PRESENT_SCALED_MAX: the tap arithmetic is 32-bit
+hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, int out_w, int out_h, int top_down,
+                                 hipStream_t stream) {
+  if (!image || !out || W < 1 || R < 1 || out_w < 1 || out_h < 1 || W > kScaledMax || R > kScaledMax ||
+      out_w > kScaledMax || out_h > kScaledMax || ((uintptr_t)out & 3))
+    return hipErrorInvalidValue;
+  const int wide = out_w % 4 == 0 && ((uintptr_t)out & 15) == 0;
+  const int units = wide ? out_w / 4 : out_w;
+  const int gx = (units + 255) / 256;
+  const int per = kScaledBlocks / gx > 0 ? kScaledBlocks / gx : 1;
+  const int gy = out_h < per ? out_h : per;
+  hipLaunchKernelGGL(present_scaled_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, stream, image, W, R,
+                     (unsigned*)out, out_w, out_h, top_down, wide);
+  return hipGetLastError();
+}
+
 // The production launch of `program` (rt_kernels.hip's launch_program; the A/B tools library
 // falls back to it): q = p with the derived table pointers and launch constants.
 inline FrameParams launch_params(const FrameParams& p) {

@@ -168,6 +168,13 @@ struct rt_ctx {
   unsigned char* d_present_own = nullptr;
   unsigned char* d_present_bound = nullptr;  // rt_bind_present (the caller's), else nullptr
   unsigned char* d_present = nullptr;        // where the last present wrote (nullptr before the first)
+  // rt_present_scaled: the image at window size, [scaled_h][scaled_w] RGBA8; the own buffer exists
+  // from the first scaled present that needs it and is replaced by one that needs more bytes
+  unsigned char* d_scaled_own = nullptr;
+  size_t scaled_own_bytes = 0;
+  unsigned char* d_scaled_bound = nullptr;   // rt_bind_present_scaled (the caller's), else nullptr
+  unsigned char* d_scaled = nullptr;         // where the last scaled present wrote
+  int scaled_w = 0, scaled_h = 0;            // its size
   std::vector<float> header;   // host copy of the SSBO prefix
   std::vector<float4> table;   // host copy of the device table (rt::table_vec4 float4)
   bool have_header = false;
@@ -316,6 +323,7 @@ void free_all(rt_ctx* c) {
   for (auto p : c->dep) if (p) (void)hipFree(p);
   if (c->d_image_own) (void)hipFree(c->d_image_own);
   if (c->d_present_own) (void)hipFree(c->d_present_own);
+  if (c->d_scaled_own) (void)hipFree(c->d_scaled_own);
   for (int k = 0; k < kAoStreams; ++k) {
     if (c->d_shapes_buf[k]) (void)hipFree(c->d_shapes_buf[k]);
   }
@@ -1697,6 +1705,83 @@ int rt_download_rgba8(rt_ctx* c, int top_down, uint8_t* out) {
   if (rc == RT_OK) rc = sync_all(c);
   if (rc != RT_OK) return rc;
   RT_HIP(c, hipMemcpyAsync(out, c->d_present, (size_t)c->own_rows * c->cfg.width * 4, hipMemcpyDeviceToHost, c->stream));
+  RT_HIP(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- the blit at window size (src/main.cpp:381-388, 783-797) --------------------------------
+// the filter reads rows above and below an output row's: whole-frame contexts only
+static bool whole_frame(const rt_ctx* c) { return c->own0 == 0 && c->own_rows == c->cfg.height; }
+static bool scaled_size_ok(int w, int h) {
+  return w >= 1 && h >= 1 && w <= RT_PRESENT_SCALED_MAX && h <= RT_PRESENT_SCALED_MAX;
+}
+
+int rt_present_scaled(rt_ctx* c, int out_width, int out_height, int top_down) {
+  if (!c || !scaled_size_ok(out_width, out_height)) return RT_E_INVAL;
+  if (!whole_frame(c)) return RT_E_STATE;
+  RT_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)rt_image_stream(c);  // as rt_present: after the image's writer, before the next
+  const size_t bytes = (size_t)out_width * out_height * 4;
+  unsigned char* dst = c->d_scaled_bound;
+  if (!dst) {
+    if (c->scaled_own_bytes < bytes) {
+      if (c->d_scaled_own) {
+        // a larger window: scaled presents already enqueued still write the old buffer, each on
+        // one of the context's streams, so all of them are waited for before it is freed
+        int rc = join(c);
+        if (rc == RT_OK) rc = sync_all(c);
+        if (rc != RT_OK) return rc;
+        if (c->d_scaled == c->d_scaled_own) c->d_scaled = nullptr;
+        RT_HIP(c, hipFree(c->d_scaled_own));
+        c->d_scaled_own = nullptr;
+        c->scaled_own_bytes = 0;
+        st = (hipStream_t)rt_image_stream(c);
+      }
+      hipError_t e = hipMalloc(&c->d_scaled_own, bytes);
+      if (e == hipErrorOutOfMemory) {
+        c->last_hip = (int)e;
+        c->d_scaled_own = nullptr;
+        return RT_E_NOMEM;
+      }
+      RT_HIP(c, e);
+      c->scaled_own_bytes = bytes;
+      RT_HIP(c, hipMemsetAsync(c->d_scaled_own, 0, bytes, st));
+    }
+    dst = c->d_scaled_own;
+  }
+  RT_HIP(c, rt::launch_present_scaled(c->d_image, c->cfg.width, c->cfg.height, dst, out_width, out_height,
+                                      top_down != 0, st));
+  c->d_scaled = dst;
+  c->scaled_w = out_width;
+  c->scaled_h = out_height;
+  return RT_OK;
+}
+
+void* rt_present_scaled_device_ptr(rt_ctx* c) { return c ? (void*)c->d_scaled : nullptr; }
+
+int rt_present_scaled_size(rt_ctx* c, int* out_width, int* out_height) {
+  if (!c) return RT_E_INVAL;
+  if (!whole_frame(c) || !c->d_scaled) return RT_E_STATE;
+  if (out_width) *out_width = c->scaled_w;
+  if (out_height) *out_height = c->scaled_h;
+  return RT_OK;
+}
+
+int rt_bind_present_scaled(rt_ctx* c, void* p) {
+  if (!c || ((uintptr_t)p & 3)) return RT_E_INVAL;  // the kernel stores whole pixels
+  if (!whole_frame(c)) return RT_E_STATE;
+  c->d_scaled_bound = (unsigned char*)p;
+  return RT_OK;
+}
+
+int rt_download_rgba8_scaled(rt_ctx* c, int out_width, int out_height, int top_down, uint8_t* out) {
+  if (!c || !out) return RT_E_INVAL;
+  RT_HIP(c, hipSetDevice(c->device));
+  int rc = rt_present_scaled(c, out_width, out_height, top_down);
+  if (rc == RT_OK) rc = join(c);
+  if (rc == RT_OK) rc = sync_all(c);
+  if (rc != RT_OK) return rc;
+  RT_HIP(c, hipMemcpyAsync(out, c->d_scaled, (size_t)out_width * out_height * 4, hipMemcpyDeviceToHost, c->stream));
   RT_HIP(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }

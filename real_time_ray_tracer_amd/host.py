@@ -342,6 +342,38 @@ class Renderer:
         self._c(self._lib.rt_bind_present(self.ctx, C.c_void_p(device_ptr) if device_ptr else None),
                 "rt_bind_present")
 
+    # 8-bit display output at window size (the blit's GL_LINEAR scaling, src/main.cpp:381-388, 783-797)
+    def present_scaled(self, out_w: int, out_h: int, top_down: bool = True):
+        """Enqueue the bilinear blit of the current image into an [out_h][out_w] RGBA8 buffer
+        (rt_present_scaled) behind the launch that wrote it; returns without waiting.  Whole-frame
+        contexts only."""
+        self._c(self._lib.rt_present_scaled(self.ctx, int(out_w), int(out_h), int(bool(top_down))),
+                "rt_present_scaled")
+
+    def image8_scaled(self, out_w: int, out_h: int, top_down: bool = True) -> np.ndarray:
+        """present_scaled + wait + copy (rt_download_rgba8_scaled): uint8 [out_h][out_w][4], equal to
+        resample_rgba8(self.image(), out_w, out_h, top_down)."""
+        out = np.empty((max(0, int(out_h)), max(0, int(out_w)), 4), np.uint8)
+        self._c(self._lib.rt_download_rgba8_scaled(self.ctx, int(out_w), int(out_h), int(bool(top_down)),
+                                                   out.ctypes.data_as(C.c_void_p)), "rt_download_rgba8_scaled")
+        return out
+
+    def present_scaled_device_ptr(self) -> int:
+        """Where the last scaled present wrote (RGBA8 on the device); 0 before the first."""
+        return self._lib.rt_present_scaled_device_ptr(self.ctx) or 0
+
+    def present_scaled_size(self) -> tuple[int, int]:
+        """(out_w, out_h) of the last scaled present (rt_present_scaled_size)."""
+        w, h = C.c_int(), C.c_int()
+        self._c(self._lib.rt_present_scaled_size(self.ctx, C.byref(w), C.byref(h)), "rt_present_scaled_size")
+        return w.value, h.value
+
+    def bind_present_scaled(self, device_ptr: int | None):
+        """Later scaled presents write into a caller-owned device buffer of out_w*out_h*4 bytes for
+        every size presented (None: the context's own)."""
+        self._c(self._lib.rt_bind_present_scaled(self.ctx, C.c_void_p(device_ptr) if device_ptr else None),
+                "rt_bind_present_scaled")
+
     # host-buffer parity path (the reference's call shape)
     def compute_one_shader(self, ssbo: SSBO, frame_num: int, program: int, image: np.ndarray | None = None) -> int:
         return self._c(self._lib.rt_compute_one_shader(self.ctx, ssbo.data.ctypes.data_as(C.c_void_p), frame_num,
@@ -538,6 +570,16 @@ class StripGroup:
     def rgba8_device_ptr(self) -> int:
         return self._lib.rt_group_rgba8_device_ptr(self.g) or 0
 
+    def image8_scaled(self, out_w: int, out_h: int, top_down: bool = True) -> np.ndarray:
+        """The assembled float frame through the bilinear blit (rt_group_download_rgba8_scaled): uint8
+        [out_h][out_w][4], equal to resample_rgba8(self.image(), out_w, out_h, top_down); raises
+        while enable_rgba8 is on."""
+        out = np.empty((max(0, int(out_h)), max(0, int(out_w)), 4), np.uint8)
+        self._c(self._lib.rt_group_download_rgba8_scaled(self.g, int(out_w), int(out_h), int(bool(top_down)),
+                                                         out.ctypes.data_as(C.c_void_p)),
+                "rt_group_download_rgba8_scaled")
+        return out
+
     def balance(self, header: Header, mode: int, rounds: int = 3) -> list[float]:
         """Cost-balance the strips (probe frame + `rounds` timed plans); returns the kept plan's
         per-strip ms per frame.  The strips restart with fresh rings."""
@@ -556,6 +598,20 @@ def quantize_rgba8(image, top_down: bool = True) -> np.ndarray:
     out = np.empty(im.shape, np.uint8)
     _check(_lib.load().rt_quantize_rgba8(fptr(im), im.shape[1], im.shape[0], int(bool(top_down)),
                                          out.ctypes.data_as(C.c_void_p)), "rt_quantize_rgba8")
+    return out
+
+
+def resample_rgba8(image, out_w: int, out_h: int, top_down: bool = True) -> np.ndarray:
+    """rt_resample_rgba8 (host only): float32 [R][W][4] -> uint8 [out_h][out_w][4], the image sampled
+    bilinearly with clamped edges as the reference's blit samples its texture, then quantize_rgba8's
+    conversion; the specification of Renderer.present_scaled (the rule: include/rt/abi.h).  top_down:
+    output row 0 is the top row."""
+    im = np.ascontiguousarray(image, np.float32)
+    if im.ndim != 3 or im.shape[2] != 4:
+        raise ValueError(f"resample_rgba8: need an [R][W][4] image, got shape {im.shape}")
+    out = np.empty((max(0, int(out_h)), max(0, int(out_w)), 4), np.uint8)
+    _check(_lib.load().rt_resample_rgba8(fptr(im), im.shape[1], im.shape[0], int(out_w), int(out_h),
+                                         int(bool(top_down)), out.ctypes.data_as(C.c_void_p)), "rt_resample_rgba8")
     return out
 
 
