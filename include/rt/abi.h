@@ -183,6 +183,14 @@ int rt_debug_cull_cache_cap(rt_ctx* ctx, size_t bytes);
  * size in bytes, 0 for an invalid configuration or header.  Two launches share a table iff their
  * keys are equal.  Never touches the GPU. */
 size_t rt_cull_key(const rt_config* cfg, const void* header, size_t header_bytes, void* key, size_t key_cap);
+/* The bounce-ray clusters that an upload of `header` builds for a context created with `cfg` (the
+ * AO kernel's later bounce rounds skip a cluster whose ball a ray provably misses).  Returns the
+ * cluster count n, 0 when the cull is off for this scene, -1 for an invalid configuration or header
+ * or when n > cap.  clusters[4k .. 4k+3] = cluster k's (centre, R); masks = [1 + n][4] words over the
+ * sphere indices: row 0 the spheres tested in every round, row 1 + k cluster k's members.  masks
+ * needs (1 + cap) * 4 words; row 0 is written when n = 0 too.  Never touches the GPU. */
+int rt_cluster_table(const rt_config* cfg, const void* header, size_t header_bytes, float* clusters, uint64_t* masks,
+                     int cap);
 /* Copy device state to the host in the REFERENCE layout.  Any pointer may be NULL.
  * pixels/normals/depth: [F][W][R] vec4 (x-major, y fastest; R = rows of this context),
  * image: [R][W] rgba32f (row 0 = row_begin, bottom-left origin like the GL texture). */
@@ -446,9 +454,34 @@ enum {
                              kernels decide it: in = (light - pos).xyz, t quads; l =
                              normalize(light - pos), len = length(light - pos); out = (l.xyz,
                              len, 1 if t > 0.0001 && length(dvec3(t * l)) < len else 0)     */,
-  RT_MATH_SIN_TABLE = 11  /* the sin's exception table (rt_sin_table.h) on this build's device code:
+  RT_MATH_SIN_TABLE = 11, /* the sin's exception table (rt_sin_table.h) on this build's device code:
                              out[2i] = 1 if entry i's binary64 sin is flagged ambiguous (so the
                              table decides it), 0 if not, -1 past the table; out[2i+1] = its x */
+  /* The kernels' conservative culls, each beside the exact test it lets them skip: the production
+   * device functions themselves on the case's operands.  Decisions are 0.0 / 1.0; an accepted t is
+   * that of a scan that starts at t = -1, so -1 = not accepted.  VIEW below = camera 3, llc_minus_
+   * campos 3, horizontal 3, vertical 3, W, H, xmin, xmax, ymin, ymax (the pixel rectangle, inclusive),
+   * hp, vp (the ray's screen position) = 20 floats. */
+  RT_MATH_CULL_CAMERA = 12, /* one lane per case.  in: VIEW, sphere 4 = 24 floats.  out 7: dir 3 =
+                             the primary direction at (hp, vp); miss = the rectangle's camera cone
+                             excludes the sphere; t_ref = sphere_eval_ray(camera, dir); t_ao, t_p = the
+                             t accepted from the sphere's camera-relative row at thresholds 0.0001, 0 */
+  RT_MATH_CULL_PLANE = 13,  /* one lane per case.  in: VIEW, (n, 0), (p0, 0) = 28 floats.  out 2: miss
+                             = the camera cone excludes the plane; t = plane_eval_ray(camera, dir)    */
+  RT_MATH_CULL_BOUNCE = 14, /* one wavefront per case.  in: sphere 4, then per lane origin 3,
+                             direction 3, live (non-zero) = 452 floats; at least one lane live.  out,
+                             5 per lane = 320: miss = the live lanes' bounce cone excludes the sphere;
+                             keep = its form with the pre-test row; pass = the lane's own pre-test
+                             on that row (0 on lanes that are not live); t accepted at 0.0001; the t
+                             that the batched first bounce's form accepts, the lanes with pass only  */
+  RT_MATH_CULL_CLUSTER = 15, /* one lane per case, n a multiple of 64.  in: origin 3, direction 3,
+                             cluster (centre, R) 4, member sphere 4 = 14 floats.  out 3: may = the
+                             ray may hit the cluster; the lane's bit of the wave-mask form of the
+                             same test; the member's t accepted at 0.0001                          */
+  RT_MATH_CULL_SHADOW = 16  /* one wavefront per case.  in: light 3, sphere 4, then per lane shaded
+                             point 3, need (non-zero) = 263 floats; at least one lane in need.  out,
+                             2 per lane = 128: keep = the cone at the light over the needing lanes
+                             does not exclude the sphere; occ = the lane's shadow ray is occluded   */
 };
 int rt_selftest_math(rt_ctx* ctx, int fn, const float* in, float* out, size_t n);
 

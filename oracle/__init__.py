@@ -89,6 +89,13 @@ def load():
     lib.rto_sphere_del.restype = C.c_float
     lib.rto_primary_dir.argtypes = [fp, C.c_float, C.c_float, fp]
     lib.rto_primary_dir.restype = None
+    for name, nptr in (("rto_sphere_eval_n", 3), ("rto_normalize3_n", 1), ("rto_primary_dir_n", 3),
+                       ("rto_plane_eval_n", 4), ("rto_shadow_occludes_n", 3)):
+        if not hasattr(lib, name):  # (older builds, as above)
+            continue
+        f = getattr(lib, name)
+        f.argtypes = [fp] * nptr + [C.c_size_t, fp]
+        f.restype = None
     _lib = lib
     return lib
 
@@ -175,6 +182,53 @@ def primary_dir(header: np.ndarray, hp, vp) -> np.ndarray:
     load().rto_primary_dir(_fp(np.ascontiguousarray(header, np.float32)), float(np.float32(hp)), float(np.float32(vp)),
                            _fp(out))
     return out
+
+
+def _rows(a, w) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, w))
+
+
+def sphere_eval_n(pos, dir_, sph) -> np.ndarray:
+    """sphere_eval of n rows: pos [n][3], dir [n][3], sph [n][4] = (centre, r)."""
+    pos, dir_, sph = _rows(pos, 3), _rows(dir_, 3), _rows(sph, 4)
+    assert len(pos) == len(dir_) == len(sph)
+    out = np.empty(len(pos), np.float32)
+    load().rto_sphere_eval_n(_fp(pos), _fp(dir_), _fp(sph), len(pos), _fp(out))
+    return out
+
+
+def normalize3_n(v) -> np.ndarray:
+    v = _rows(v, 3)
+    out = np.empty_like(v)
+    load().rto_normalize3_n(_fp(v), len(v), _fp(out))
+    return out
+
+
+def primary_dir_n(view, hp, vp) -> np.ndarray:
+    """primary_dir of n rows: view [n][9] = (llc_minus_campos, horizontal, vertical), hp [n], vp [n]."""
+    view = _rows(view, 9)
+    hp, vp = _rows(hp, 1), _rows(vp, 1)
+    assert len(view) == len(hp) == len(vp)
+    out = np.empty((len(view), 3), np.float32)
+    load().rto_primary_dir_n(_fp(view), _fp(hp), _fp(vp), len(view), _fp(out))
+    return out
+
+
+def plane_eval_n(pos, dir_, nrm, p0) -> np.ndarray:
+    pos, dir_, nrm, p0 = _rows(pos, 3), _rows(dir_, 3), _rows(nrm, 3), _rows(p0, 3)
+    assert len(pos) == len(dir_) == len(nrm) == len(p0)
+    out = np.empty(len(pos), np.float32)
+    load().rto_plane_eval_n(_fp(pos), _fp(dir_), _fp(nrm), _fp(p0), len(pos), _fp(out))
+    return out
+
+
+def shadow_occludes_n(light, pos, sph) -> np.ndarray:
+    """shadow_ray's decision for one sphere per (light, pos) row: True when it occludes."""
+    light, pos, sph = _rows(light, 3), _rows(pos, 3), _rows(sph, 4)
+    assert len(light) == len(pos) == len(sph)
+    out = np.empty(len(pos), np.float32)
+    load().rto_shadow_occludes_n(_fp(light), _fp(pos), _fp(sph), len(pos), _fp(out))
+    return out != 0
 
 
 def nthreads_default() -> int:

@@ -86,6 +86,14 @@ void rto_normalize3(const float v[3], float out[3]);
  * tests to construct exactly tangent rays (del == 0) */
 float rto_sphere_del(const float pos[3], const float dir[3], const float center[3], float r);
 void rto_primary_dir(const float* header, float hp, float vp, float out[3]);
+/* the same primitives on n rows (pos / dir / normal / p0 / light rows of 3, sphere rows of
+ * (centre, r), view rows of llc_minus_campos, horizontal, vertical), and shadow_ray's decision for
+ * one sphere per (light, pos) row: 1.0f when it occludes */
+void rto_sphere_eval_n(const float* pos, const float* dir, const float* sph, size_t n, float* out);
+void rto_normalize3_n(const float* v, size_t n, float* out);
+void rto_primary_dir_n(const float* view, const float* hp, const float* vp, size_t n, float* out);
+void rto_plane_eval_n(const float* pos, const float* dir, const float* nrm, const float* p0, size_t n, float* out);
+void rto_shadow_occludes_n(const float* light, const float* pos, const float* sph, size_t n, float* out);
 
 #ifdef __cplusplus
 }

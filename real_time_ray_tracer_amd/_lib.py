@@ -22,7 +22,8 @@ RT_PROG_H_COMPUTE = 5
 RT_MODE_AO_PP, RT_MODE_AO, RT_MODE_PHONG, RT_MODE_PHONG_REFL = 1, 2, 3, 4
 (RT_MATH_SIN, RT_MATH_RANDOM, RT_MATH_SQRT, RT_MATH_DIV, RT_MATH_NORMALIZE, RT_MATH_SPHERE, RT_MATH_SQRT_SWEEP,
  RT_MATH_RCP_SWEEP, RT_MATH_SQRT_TAIL_SWEEP, RT_MATH_SIN_RANGE, RT_MATH_SHADOW,
- RT_MATH_SIN_TABLE) = range(12)
+ RT_MATH_SIN_TABLE, RT_MATH_CULL_CAMERA, RT_MATH_CULL_PLANE, RT_MATH_CULL_BOUNCE, RT_MATH_CULL_CLUSTER,
+ RT_MATH_CULL_SHADOW) = range(17)
 RT_NUM_FRAMES = 8
 RT_RECURSION_DEPTH = 20
 RT_SHAPE_SPHERE, RT_SHAPE_RECTANGLE, RT_SHAPE_PLANE = 1, 3, 5
@@ -66,6 +67,7 @@ SIGNATURES = {
     "rt_cull_cache_frame_bytes": (C.c_size_t, [_ctx]),
     "rt_debug_cull_cache_cap": (C.c_int, [_ctx, C.c_size_t]),
     "rt_cull_key": (C.c_size_t, [C.POINTER(rt_config), _vp, C.c_size_t, _vp, C.c_size_t]),
+    "rt_cluster_table": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, C.POINTER(C.c_uint64), C.c_int]),
     "rt_download": (C.c_int, [_ctx, _fp, _fp, _fp, _fp]),
     "rt_download_rect": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     "rt_upload_gbuffer": (C.c_int, [_ctx, _fp, _fp, _fp]),

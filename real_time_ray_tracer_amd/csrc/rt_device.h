@@ -134,13 +134,27 @@ __device__ __forceinline__ float sqrt_rn_core(float x) {
 // of b, so fl(-b + s) and fl(-b - s) are both -b whatever s is; with |b| < 2^-22 both roots
 // are below 2.4e-7 in magnitude and never pass the threshold.  Accepted t and index are
 // therefore unchanged.  (x = +inf, a discriminant that overflowed — |b| > 2^64 — gives NaN,
-// which the caller rejects, where sqrt_rn gives +inf.)
+// where sqrt_rn gives +inf: the sphere candidates take sqrt_rn_tail_inf below; a shadow ray's
+// decision is the same either way, t = +inf never being nearer than the light.)
 // (The clamp is one v_max_f32 written out: fmaxf adds a canonicalising v_max in front of it,
 // which buys nothing here, x being a non-negative discriminant and never NaN.)
 __device__ __forceinline__ float sqrt_rn_tail(float x) {
   float xc;
   asm("v_max_f32_e32 %0, 0x0d800000, %1" : "=v"(xc) : "v"(x));  // max(x, 2^-100)
   return sqrt_rn_core(xc);
+}
+
+// sqrt_rn_tail for the discriminant of a sphere candidate, exact at +inf too (a radius of +-inf, or
+// a discriminant that overflowed): sqrt_rn_core gives NaN there, and a NaN root rejects a sphere
+// that sphere_eval_ray reports at t = +inf, which the reference's scan accepts.  One v_mul and one
+// v_max: for every finite x <= FLT_MAX < 2^252, sqrt(x) > x * 2^-126, so the max returns the root
+// (below 2^-100 the product is 0 and the root is >= 0); at +inf the product is +inf and v_max_f32
+// returns it over the NaN.  (Written out for the reason given at sqrt_rn_tail's clamp.)
+__device__ __forceinline__ float sqrt_rn_tail_inf(float x) {
+  const float s = sqrt_rn_tail(x), big = x * 0x1p-126f;
+  float r;
+  asm("v_max_f32_e32 %0, %1, %2" : "=v"(r) : "v"(big), "v"(s));
+  return r;
 }
 
 // sin of N arguments at once (tier 1 above), the same operations per argument: each binary64 constant is
@@ -361,7 +375,7 @@ __device__ __forceinline__ void sphere_candidate(f3 pos, f3 dir, float4 g, int i
     // -b, so the reference's (del == 0 ? -b : root choice) differs only in values <= 0, and
     // (t2 < 0 ? t1 : t2) differs from (t2 < 0 ? (t1 < 0 ? -1 : t1) : t2) only when t1 < 0:
     // none of these is ever accepted (thr > 0).  Accepted t and index are unchanged.
-    float s = thr >= 1e-6f ? sqrt_rn_tail(del) : sqrt_rn(del);  // thr is a literal at every call
+    float s = thr >= 1e-6f ? sqrt_rn_tail_inf(del) : sqrt_rn(del);  // thr is a literal at every call
     float t1 = -1.0f * b + s;
     float t2 = -1.0f * b - s;
     // (t2 < 0 ? t1 : t2) as an unsigned min of the bits: t1 >= t2, so for t2 >= 0 both are
@@ -388,7 +402,7 @@ __device__ __forceinline__ void sphere_candidate_rel(f3 dir, float4 q, float r, 
   const bool hit = del >= 0.0f;
   if (__builtin_amdgcn_ballot_w64(hit) != 0) {
     // the tail of sphere_candidate (see there)
-    float s = thr >= 1e-6f ? sqrt_rn_tail(del) : sqrt_rn(del);
+    float s = thr >= 1e-6f ? sqrt_rn_tail_inf(del) : sqrt_rn(del);
     float t1 = -1.0f * b + s;
     float t2 = -1.0f * b - s;
     float res = __uint_as_float(min(__float_as_uint(t1), __float_as_uint(t2)));
@@ -415,7 +429,7 @@ __device__ __forceinline__ void sphere_candidate_if(f3 pos, f3 dir, float4 g, in
     // -b, so the reference's (del == 0 ? -b : root choice) differs only in values <= 0, and
     // (t2 < 0 ? t1 : t2) differs from (t2 < 0 ? (t1 < 0 ? -1 : t1) : t2) only when t1 < 0:
     // none of these is ever accepted (thr > 0).  Accepted t and index are unchanged.
-    float s = thr >= 1e-6f ? sqrt_rn_tail(del) : sqrt_rn(del);  // thr is a literal at every call
+    float s = thr >= 1e-6f ? sqrt_rn_tail_inf(del) : sqrt_rn(del);  // thr is a literal at every call
     float t1 = -1.0f * b + s;
     float t2 = -1.0f * b - s;
     // (t2 < 0 ? t1 : t2) as an unsigned min of the bits: t1 >= t2, so for t2 >= 0 both are

@@ -539,7 +539,8 @@ __device__ __forceinline__ ConeF wave_tile_cone(const FrameParams& P, int bx, in
 // shadow_ray (p_compute.glsl:145-166) for the whole wave at once, all-sphere scenes: every
 // shadow line passes (within ~3e-5) through the light, so the lines of the lanes that need
 // one lie in a cone with its apex at the light.  Spheres outside that cone (radius inflated
-// by 1e-4 plus cone_misses_f's margins) are missed by every line (-1, never an occluder); the
+// for the longest line's rounding and by 1e-4, shadow_cone_keeps, plus cone_misses_f's margins)
+// are missed by every line (-1, never an occluder); the
 // rest are tested as shadow_lit does.  "Some occluder exists" does not depend on the order.
 // Must be called by every lane of the wave (ballots and shuffles).
 #ifndef RT_SHADOW_CONE_MIN
@@ -553,6 +554,36 @@ __device__ __forceinline__ bool shadow_occludes(float tf, f3 l, double dlen) {
   const double t = (double)tf;
   const double dx = t * (double)l.x, dy = t * (double)l.y, dz = t * (double)l.z;
   return sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) < dlen;
+}
+// The cone at the light over the directions -l of the lanes that need a shadow ray (DPP
+// reductions; the cone only has to contain every lane's direction, whatever the sum order), and
+// lmax, the longest of their lines (len = |light - pos|).  Must be called by every lane of the wave.
+__device__ __forceinline__ ConeF shadow_cone(bool need, f3 l, float len, float& lmax) {
+  lmax = wave_max_f(need ? len : 0.0f);
+  const float sx = wave_sum_f(need ? -l.x : 0.0f), sy = wave_sum_f(need ? -l.y : 0.0f),
+              sz = wave_sum_f(need ? -l.z : 0.0f);
+  const float il = __builtin_amdgcn_rsqf(sx * sx + sy * sy + sz * sz);
+  ConeF cone;
+  cone.ax = sx * il; cone.ay = sy * il; cone.az = sz * il;
+  float cd = wave_min_f(need ? -(cone.ax * l.x + cone.ay * l.y + cone.az * l.z) : 1.0f);
+  cd = fminf(fmaxf(cd - 2e-5f, -1.0f), 1.0f);
+  cone.ct = cd;
+  cone.st = __builtin_amdgcn_sqrtf(fmaxf(0.0f, 1.0f - cd * cd));
+  return cone;
+}
+// A sphere row that the shadow cone does not exclude (wide: the cone is nearly a half-space).
+// A shadow ray starts at the shaded point, up to Lmax = lmax + |c - light| from the sphere's centre,
+// and its computed discriminant errs by ~7e-7 Lmax^2 whatever the sphere's distance D from the
+// light; cone_misses_f's own inflation, 1e-5 (D^2 + r^2), covers that for rays from the apex only.
+// So the radius tested is r' = sqrt(r^2 + 1e-5 Lmax^2) (1 + 1e-5) + 1e-4: a line that passes at r'
+// or more has an exact discriminant <= -1e-5 Lmax^2, 14x the error, as in bounce_cone_misses.  With
+// D alone a small sphere next to the light was culled while the reference's own rounding reported it
+// as the occluder of points 20 D and more away (tests/test_gpu_culls.py, the long-line cases).
+__device__ __forceinline__ bool shadow_cone_keeps(const ConeF& cone, bool wide, float4 g, f3 light, float lmax) {
+  const float vx = g.x - light.x, vy = g.y - light.y, vz = g.z - light.z;
+  const float Lm = lmax + fast_sqrt(vx * vx + vy * vy + vz * vz);
+  const float rr = fast_sqrt(g.w * g.w + 1e-5f * (Lm * Lm)) * 1.00001f + 1e-4f;
+  return wide || !cone_misses_f(cone, make_float4(g.x, g.y, g.z, rr), light.x, light.y, light.z);
 }
 // PL: planes occlude too (any shape type does, p_compute.glsl:153); they are tested after the
 // spheres ("some occluder exists" does not depend on the order).
@@ -575,18 +606,9 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
     }
     return lit;
   }
-  // cone at the light over the directions -l of the lanes that need a shadow ray (DPP
-  // reductions; the cone only has to contain every lane's direction, whatever the sum order)
-  const float sx = wave_sum_f(need ? -l.x : 0.0f), sy = wave_sum_f(need ? -l.y : 0.0f),
-              sz = wave_sum_f(need ? -l.z : 0.0f);
-  const float il = __builtin_amdgcn_rsqf(sx * sx + sy * sy + sz * sz);
-  ConeF cone;
-  cone.ax = sx * il; cone.ay = sy * il; cone.az = sz * il;
-  float cd = wave_min_f(need ? -(cone.ax * l.x + cone.ay * l.y + cone.az * l.z) : 1.0f);
-  cd = fminf(fmaxf(cd - 2e-5f, -1.0f), 1.0f);
-  cone.ct = cd;
-  cone.st = __builtin_amdgcn_sqrtf(fmaxf(0.0f, 1.0f - cd * cd));
-  const bool wide = !(cd > 0.05f);  // nearly a half-space: test everything
+  float lmax;
+  const ConeF cone = shadow_cone(need, l, len, lmax);
+  const bool wide = !(cone.ct > 0.05f);  // nearly a half-space: test everything
   const int lane = threadIdx.x & 63;
   auto word = [&](int w, bool keep) {
     unsigned long long m = uniform_mask(__ballot(keep));
@@ -596,9 +618,7 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
       if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, gw[j]), l, dlen)) lit = false;
     }
   };
-  auto keep_row = [&](float4 g) {
-    return wide || !cone_misses_f(cone, make_float4(g.x, g.y, g.z, g.w + 1e-4f), light.x, light.y, light.z);
-  };
+  auto keep_row = [&](float4 g) { return shadow_cone_keeps(cone, wide, g, light, lmax); };
   int w = 0;
   if (pre0) {  // the first word's rows, already requested by the caller (n > kShadowConeMinObj here)
     word(0, lane < n && keep_row(*pre0));
@@ -2289,10 +2309,118 @@ __device__ __forceinline__ void post_pixel(const FrameParams& P, int x, int y, u
 // ---------------------------------------------------------------------------------------
 // math self-test
 // ---------------------------------------------------------------------------------------
+// The view of the cull self-tests (RT_MATH_CULL_CAMERA / _PLANE): the FrameParams fields that
+// pool_cone_f and primary_dir read, from a[3..13] = llc_minus_campos, horizontal, vertical, W, H.
+__device__ __forceinline__ void selftest_view(FrameParams& P, const float* a) {
+  P.lx = a[3]; P.ly = a[4]; P.lz = a[5];
+  P.hx = a[6]; P.hy = a[7]; P.hz = a[8];
+  P.vx = a[9]; P.vy = a[10]; P.vz = a[11];
+  P.fW = a[12]; P.fH = a[13];
+}
+
+// Cases of the wave-per-case functions (their 64 lanes share ballots and DPP reductions).
+__host__ __device__ constexpr bool selftest_wave_fn(int fn) { return fn == 14 || fn == 16; }
+
 __global__ void selftest_kernel(int fn, const float* __restrict__ in, float* __restrict__ out, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (selftest_wave_fn(fn)) i >>= 6;  // one wave per case: the exit below is wave-uniform
   if (i >= n) return;
   switch (fn) {
+    case 12: {  // camera-ray cone vs sphere, and the exact sphere test's forms
+      const float* a = in + 24 * i;
+      FrameParams P;
+      selftest_view(P, a);
+      const f3 cam = mk(a[0], a[1], a[2]);
+      const float4 g = make_float4(a[20], a[21], a[22], a[23]);
+      const ConeF cone = pool_cone_f(P, (int)a[14], (int)a[15], (int)a[16], (int)a[17]);
+      const f3 dir = primary_dir(P, a[18], a[19]);
+      // the sphere's camera-relative row as rt_shim pack_header forms it
+      const float px = cam.x - g.x, py = cam.y - g.y, pz = cam.z - g.z;
+      const float4 q = make_float4(px, py, pz, fmaf(pz, pz, fmaf(py, py, px * px)));
+      float t_ao = -1.0f, t_p = -1.0f;
+      int ind = -1;
+      sphere_candidate_rel(dir, q, g.w, 0, 0.0001f, t_ao, ind);
+      sphere_candidate_rel(dir, q, g.w, 0, 0.0f, t_p, ind);
+      float* o = out + 7 * i;
+      o[0] = dir.x; o[1] = dir.y; o[2] = dir.z;
+      o[3] = cone_misses_f(cone, g, cam.x, cam.y, cam.z) ? 1.0f : 0.0f;
+      o[4] = sphere_eval(cam, dir, g);
+      o[5] = t_ao;
+      o[6] = t_p;
+      break;
+    }
+    case 13: {  // camera-ray cone vs plane
+      const float* a = in + 28 * i;
+      FrameParams P;
+      selftest_view(P, a);
+      const f3 cam = mk(a[0], a[1], a[2]);
+      const float4 pa = make_float4(a[20], a[21], a[22], a[23]), pb = make_float4(a[24], a[25], a[26], a[27]);
+      const ConeF cone = pool_cone_f(P, (int)a[14], (int)a[15], (int)a[16], (int)a[17]);
+      const f3 dir = primary_dir(P, a[18], a[19]);
+      out[2 * i] = plane_cone_misses(cone, pa, pb, cam) ? 1.0f : 0.0f;
+      out[2 * i + 1] = plane_eval(cam, dir, pa, pb);
+      break;
+    }
+    case 14: {  // first-bounce cone of one wave's rays vs sphere, and the per-ray pre-test
+      const int lane = threadIdx.x & 63;
+      const float* a = in + 452 * i;
+      const float* q = a + 4 + 7 * lane;
+      const float4 g = make_float4(a[0], a[1], a[2], a[3]);
+      const f3 p = mk(q[0], q[1], q[2]), d = mk(q[3], q[4], q[5]);
+      const bool live = q[6] != 0.0f;
+      const unsigned long long lm = __ballot(live);
+      float miss = 0.0f, keep = 1.0f, pass = 0.0f, t = -1.0f, t_if = -1.0f;
+      if (lm != 0) {  // (the kernel builds no cone for a batch without live lanes)
+        const ConeB cb = bounce_cone(live, p, d, lm);
+        float4 pt;
+        miss = bounce_cone_misses(cb, g) ? 1.0f : 0.0f;
+        keep = bounce_cone_keep_pt(cb, g, pt) ? 1.0f : 0.0f;
+        f3 tdir = d;  // NaN on the lanes that are not live, as in ao_batch_kernel
+        if (!live) tdir = mk(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000), __int_as_float(0x7fc00000));
+        pass = fmaf(tdir.z, pt.z, fmaf(tdir.y, pt.y, tdir.x * pt.x)) >= pt.w ? 1.0f : 0.0f;
+        int ind = -1, ind_if = -1;
+        sphere_candidate(p, d, g, 0, 0.0001f, t, ind);
+        // the form the batched first bounce runs: only the lanes whose pre-test passed may accept
+        const unsigned long long pm = __builtin_amdgcn_ballot_w64(pass != 0.0f);
+        if (pm != 0) sphere_candidate_if(p, d, g, 0, 0.0001f, t_if, ind_if, pm);
+      }
+      float* o = out + 320 * i + 5 * lane;
+      o[0] = miss; o[1] = keep; o[2] = pass; o[3] = t; o[4] = t_if;
+      break;
+    }
+    case 15: {  // cluster ball vs ray, both forms, and a member's exact test
+      const float* a = in + 14 * i;
+      const f3 p = mk(a[0], a[1], a[2]), d = mk(a[3], a[4], a[5]);
+      const float4 cb = make_float4(a[6], a[7], a[8], a[9]), g = make_float4(a[10], a[11], a[12], a[13]);
+      const unsigned long long m = cluster_may_hit_mask(p, d, cb);
+      float t = -1.0f;
+      int ind = -1;
+      sphere_candidate(p, d, g, 0, 0.0001f, t, ind);
+      out[3 * i] = cluster_may_hit(p, d, cb) ? 1.0f : 0.0f;
+      out[3 * i + 1] = (m >> (threadIdx.x & 63)) & 1ull ? 1.0f : 0.0f;
+      out[3 * i + 2] = t;
+      break;
+    }
+    case 16: {  // shadow cone at the light over one wave's shaded points vs sphere
+      const int lane = threadIdx.x & 63;
+      const float* a = in + 263 * i;
+      const float* q = a + 7 + 4 * lane;
+      const f3 light = mk(a[0], a[1], a[2]), pos = mk(q[0], q[1], q[2]);
+      const float4 g = make_float4(a[3], a[4], a[5], a[6]);
+      const bool need = q[3] != 0.0f;
+      // shadow_lit_cone's set-up
+      const f3 lv = light - pos;
+      const f3 l = normalize(lv);
+      const float len = sqrtf(dot(lv, lv));
+      const f3 np = pos + 0.01f * l;
+      const double dlen = (double)len;
+      float lmax;
+      const ConeF cone = shadow_cone(need, l, len, lmax);
+      const bool wide = !(cone.ct > 0.05f);
+      out[128 * i + 2 * lane] = shadow_cone_keeps(cone, wide, g, light, lmax) ? 1.0f : 0.0f;
+      out[128 * i + 2 * lane + 1] = shadow_occludes(sphere_eval_shadow(np, l, g), l, dlen) ? 1.0f : 0.0f;
+      break;
+    }
     case 0: out[i] = det_sin(in[i]); break;
     case 9: out[i] = det_sin(__uint_as_float(__float_as_uint(in[0]) + (unsigned)i)); break;  // bit patterns in[0].., wrapping
     case 1: out[i] = grandom(in[2 * i], in[2 * i + 1]); break;
@@ -2332,6 +2460,7 @@ __global__ void selftest_kernel(int fn, const float* __restrict__ in, float* __r
         const float s = sqrt_rn_tail(x);
         if (u >= 0x0f800000ull) bad += __float_as_uint(s) != __float_as_uint(sqrtf(x));
         else bad += !(s >= 0.0f && s <= 0x1p-47f);
+        bad += __float_as_uint(sqrt_rn_tail_inf(x)) != __float_as_uint(s);  // the same root on every finite float
       }
       out[i] = (float)bad;
       break;
@@ -2848,7 +2977,8 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
 
 hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  unsigned grid = (unsigned)((n + 255) / 256);
+  const size_t lanes = selftest_wave_fn(fn) ? n * 64 : n;
+  unsigned grid = (unsigned)((lanes + 255) / 256);
   hipLaunchKernelGGL(selftest_kernel, dim3(grid), dim3(256), 0, stream, fn, d_in, d_out, n);
   return hipGetLastError();
 }

@@ -232,7 +232,8 @@ size_t slot_elems(const rt_ctx* c) { return (size_t)c->band_rows * c->cfg.width;
 // One row per table beyond the shapes: the colour table's row -1 (the geo2 table's last row)
 // holds the background, so the AO kernel's shading reads a miss's attenuation as col[-1]
 // (rt_kernels_impl.h col_at) instead of keeping the background in scalar registers.
-int table_stride(const rt_ctx* c) { return std::max(1, c->cfg.num_shapes) + 1; }
+int table_stride(const rt_config& cfg) { return std::max(1, cfg.num_shapes) + 1; }
+int table_stride(const rt_ctx* c) { return table_stride(c->cfg); }
 
 hipEvent_t get_event(rt_ctx* c) {
   if (!c->event_pool.empty()) {
@@ -1198,13 +1199,13 @@ int build_clusters(const float4* sph, int nobj, float4* ctab, unsigned long long
 
 // Validate a header and pack it into the device table layout (rt::table_vec4 float4 at `tab`:
 // shape tables, sphere table, plane table, clusters, rand_buffer); sets nobj / nplanes / ncl.
-int pack_header(rt_ctx* c, const float* h, float4* tab, int& nobj, int& nplanes, int& ncl) {
-  const int S = c->cfg.num_shapes, spp = c->cfg.spp;
+int pack_header(const rt_config& cfg, const float* h, float4* tab, int& nobj, int& nplanes, int& ncl) {
+  const int S = cfg.num_shapes, spp = cfg.spp;
   const float mz = h[RT_HDR_MODE * 4 + 2];
   if (!(mz >= 0.0f && mz < (float)(S + 1))) return RT_E_INVAL;  // int(mode.z) must be in [0, S]
   nobj = (int)mz;
   const float* sh = h + rt_off_shapes() / 4;
-  const int Sc = table_stride(c);
+  const int Sc = table_stride(cfg);
   const float qnan = std::numeric_limits<float>::quiet_NaN();
   float4* sph = tab + rt::sphere_table(Sc);
   float4* pln = tab + rt::plane_table(Sc);
@@ -1268,7 +1269,7 @@ int rt_upload_header(rt_ctx* c, const void* header, size_t bytes) {
     if (!(mz >= 0.0f && mz < (float)(S + 1))) return RT_E_INVAL;
   }
   std::memcpy(c->header.data(), header, bytes);
-  int rc = pack_header(c, h, c->table.data(), nobj, np, ncl);
+  int rc = pack_header(c->cfg, h, c->table.data(), nobj, np, ncl);
   if (rc != RT_OK) return rc;
   RT_HIP(c, hipSetDevice(c->device));
   // pipelined: into the header copy of the next frame, on its AO stream (ordered after the AO
@@ -1447,7 +1448,7 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
     for (int j = 0; j < m; ++j) {
       float4* tab = c->batch_host.data() + (size_t)nd * tv;
       int rc = update(k0 + j, f);
-      if (rc == RT_OK) rc = pack_header(c, header, tab, nobj[j], npl[j], ncl[j]);
+      if (rc == RT_OK) rc = pack_header(c->cfg, header, tab, nobj[j], npl[j], ncl[j]);
       if (rc != RT_OK) return rc;
       std::memcpy(c->batch_hdr.data() + (size_t)j * hf, header, bytes);  // camera / light of frame j
       slot[j] = f;
@@ -1546,6 +1547,21 @@ size_t rt_cull_key(const rt_config* cfg, const void* header, size_t header_bytes
   if (x.row_begin == 0 && x.row_end == 0) x.row_end = x.height;  // as rt_create
   if (x.row_begin < 0 || x.row_end > x.height || x.row_begin >= x.row_end) return 0;
   return cull_key(x, (const float*)header, (unsigned char*)key, key_cap);
+}
+
+int rt_cluster_table(const rt_config* cfg, const void* header, size_t header_bytes, float* clusters, uint64_t* masks,
+                     int cap) {
+  if (!cfg || !header || !clusters || !masks || cap < 0 || cfg->spp <= 0 || cfg->num_shapes < 0 ||
+      header_bytes != rt_header_bytes(cfg->num_shapes, cfg->spp))
+    return -1;
+  // the table an upload packs (pack_header: the sphere table, then build_clusters over it)
+  std::vector<float4> tab(rt::table_vec4(table_stride(*cfg), cfg->spp));
+  int nobj = 0, np = 0, ncl = 0;
+  if (pack_header(*cfg, (const float*)header, tab.data(), nobj, np, ncl) != RT_OK || ncl > cap) return -1;
+  const int Sc = table_stride(*cfg);
+  std::memcpy(clusters, tab.data() + rt::cluster_table(Sc), (size_t)ncl * sizeof(float4));
+  std::memcpy(masks, tab.data() + rt::cluster_mask_table(Sc), (size_t)(1 + ncl) * rt::kClusterWords * sizeof(uint64_t));
+  return ncl;
 }
 
 int rt_set_frame_batch(rt_ctx* c, int max_frames) {
@@ -1919,8 +1935,10 @@ int rt_read_row_counters(rt_ctx* c, uint64_t* rows, int reset) {
 }
 
 int rt_selftest_math(rt_ctx* c, int fn, const float* in, float* out, size_t n) {
-  if (!c || !in || !out || fn < 0 || fn > RT_MATH_SIN_TABLE) return RT_E_INVAL;
-  static const int in_w[] = {1, 2, 1, 2, 3, 10, 0, 0, 0, 0, 4, 0}, out_w[] = {1, 1, 1, 1, 3, 1, 1, 1, 1, 1, 5, 2};
+  if (!c || !in || !out || fn < 0 || fn > RT_MATH_CULL_SHADOW) return RT_E_INVAL;
+  if (fn == RT_MATH_CULL_CLUSTER && n % 64 != 0) return RT_E_INVAL;  // its wave-mask form needs full waves
+  static const int in_w[] = {1, 2, 1, 2, 3, 10, 0, 0, 0, 0, 4, 0, 24, 28, 452, 14, 263},
+                   out_w[] = {1, 1, 1, 1, 3, 1, 1, 1, 1, 1, 5, 2, 7, 2, 320, 3, 128};
   RT_HIP(c, hipSetDevice(c->device));
   float *din = nullptr, *dout = nullptr;
   const bool sweep = fn == RT_MATH_SQRT_SWEEP || fn == RT_MATH_RCP_SWEEP || fn == RT_MATH_SQRT_TAIL_SWEEP ||

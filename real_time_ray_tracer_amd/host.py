@@ -130,6 +130,18 @@ class Header:
     def copy(self) -> "Header":
         return Header(self.S, self.AA, self.data.copy())
 
+    def cluster_table(self, cap: int = 64):
+        """The bounce-ray clusters an upload of this header builds (rt_cluster_table, host only):
+        (clusters [n][4] float32 (centre, R), always-tested mask [4] uint64, member masks [n][4] uint64)."""
+        cfg = _lib.rt_config(1, 1, self.S, self.AA, 1, 1, 0, 0)
+        clusters = np.zeros((cap, 4), np.float32)
+        masks = np.zeros((1 + cap, 4), np.uint64)
+        n = self._lib.rt_cluster_table(C.byref(cfg), self.data.ctypes.data_as(C.c_void_p), self.data.nbytes,
+                                       fptr(clusters), masks.ctypes.data_as(C.POINTER(C.c_uint64)), cap)
+        if n < 0:
+            raise ValueError("rt_cluster_table rejected the header or the capacity")
+        return clusters[:n].copy(), masks[0].copy(), masks[1:1 + n].copy()
+
 
 class SSBO:
     """A whole ssbo_data-layout host buffer (src/main.cpp:49-85) for the host-buffer path."""
@@ -424,9 +436,12 @@ class Renderer:
         return out
 
     def selftest_math(self, fn: int, inputs: np.ndarray, n: int) -> np.ndarray:
-        out_w = {_lib.RT_MATH_NORMALIZE: 3, _lib.RT_MATH_SHADOW: 5, _lib.RT_MATH_SIN_TABLE: 2}.get(fn, 1)
+        out_w = {_lib.RT_MATH_NORMALIZE: 3, _lib.RT_MATH_SHADOW: 5, _lib.RT_MATH_SIN_TABLE: 2,
+                 _lib.RT_MATH_CULL_CAMERA: 7, _lib.RT_MATH_CULL_PLANE: 2, _lib.RT_MATH_CULL_BOUNCE: 320,
+                 _lib.RT_MATH_CULL_CLUSTER: 3, _lib.RT_MATH_CULL_SHADOW: 128}.get(fn, 1)
         in_w = {_lib.RT_MATH_RANDOM: 2, _lib.RT_MATH_DIV: 2, _lib.RT_MATH_NORMALIZE: 3, _lib.RT_MATH_SPHERE: 10,
-                _lib.RT_MATH_SHADOW: 4}.get(fn, 1)
+                _lib.RT_MATH_SHADOW: 4, _lib.RT_MATH_CULL_CAMERA: 24, _lib.RT_MATH_CULL_PLANE: 28,
+                _lib.RT_MATH_CULL_BOUNCE: 452, _lib.RT_MATH_CULL_CLUSTER: 14, _lib.RT_MATH_CULL_SHADOW: 263}.get(fn, 1)
         inp = np.ascontiguousarray(inputs, np.float32).reshape(-1)
         sweep = fn in (_lib.RT_MATH_SQRT_SWEEP, _lib.RT_MATH_RCP_SWEEP, _lib.RT_MATH_SQRT_TAIL_SWEEP,
                        _lib.RT_MATH_SIN_RANGE, _lib.RT_MATH_SIN_TABLE)

@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--env", default="RTRT_AO_VARIANT")
     ap.add_argument("--libs", default="", help="comma-separated librtrt.so builds to compare instead of variants")
     ap.add_argument("--prog", type=int, default=0, help="program to time (default: the trace pass)")
+    ap.add_argument("--mode", type=int, default=0, help="lighting mode 1-4 in place of the config's (its scene and size kept)")
     ap.add_argument("--time-from", type=int, default=1, help="first frame timed (history fills over 8 frames)")
     ap.add_argument("--allow-diff", action="store_true", help="timing ablations: images may differ")
     ap.add_argument("--size", default="", help="WxH: the config's scene at another frame size")
@@ -45,6 +46,9 @@ def main():
                          "normals and depth compared bit for bit as well as the image")
     args = ap.parse_args()
     W, H, S, spp, mode, desc = CONFIGS[args.config]
+    if args.mode:
+        mode = args.mode
+        desc += f" [mode {mode}]"
     if args.size:
         W, H = (int(v) for v in args.size.lower().split("x"))
     variants = [v for v in args.variants.split(",")]
