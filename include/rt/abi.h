@@ -154,6 +154,31 @@ int rt_tile_schedule_state(rt_ctx* ctx);
 /* how many longest-first orders have been taken up since the schedule was (re)enabled: each new
  * order replaces a table that launches still in flight may read, so tests count the swaps */
 int rt_tile_schedule_orders(rt_ctx* ctx);
+/* Phong g-buffer: modes 3 and 4 store normals and depth as the AO programs do.  Off by default:
+ * like the reference's p_compute and h_compute, a mode-3 or mode-4 frame then writes pixels[f] and
+ * the image and leaves normals_buffer[f] and depth_buffer[f] as they were (the reference's README
+ * lists the stores as open work).  on != 0, per context:
+ *   a mode-3 (p_compute) or mode-4 (h_compute) frame on slot f writes, for every pixel (x, y) of
+ *   the rows it traces, the closest hit of the primary ray as that kernel itself found it, i.e. the
+ *   surface whose colour the pixel shows (accepted for t > 0 in mode 3, p_compute.glsl:177-188, and
+ *   for t > 0.001 in mode 4, h_compute.glsl:199-210):
+ *     hit on shape ind at t:  normals[f][x][y] = (n, 1),  depth[f][x][y] = (t, 0, 0, 1),
+ *                             n = the shading's normal of shape ind at camera + t * dir
+ *                             (a sphere: normalize(p - c); a plane: its stored normal);
+ *     miss:                   both are (0, 0, 0, 0).
+ *   An emissive flag makes no difference (modes 3 and 4 ignore it).  These are the values
+ *   ao_compute.glsl:222-229 and 249-258 write for sample 0's first segment at AA = 1.  depth.y, the
+ *   AO programs' bounce count, is 0: mode 4's mirror segments are deliberately not counted there.
+ *   Being g-buffer writers, the two programs then trace a strip context's band (the strip and its
+ *   halo rows) for pixels, normals and depth, as the AO programs do, with the image still the
+ *   strip's own rows: a strip's ring evolves like the same rows of a whole-frame ring, and a later
+ *   post-process pass reads correct neighbours.  A strip's work and row counters then include the
+ *   halo rows, as they do for the AO programs.  The colours do not depend on the switch.
+ * A change of the switch on a strip context waits for the main stream and restarts mode 4's tile
+ * schedule (a strip's tiles change with its rows); on a whole-frame context it only selects the
+ * kernels of the next launch.  RT_E_INVAL for a NULL context. */
+int rt_set_phong_gbuffer(rt_ctx* ctx, int on);
+int rt_phong_gbuffer(rt_ctx* ctx); /* 1 = on, 0 = off */
 /* Cull cache of the AO programs (modes 1 and 2), on by default.  Every pool of an AO launch starts
  * by culling the sphere table against the cone of its primary rays; that cull reads the camera,
  * the frame and strip geometry, spp, int(mode.z) and the sphere rows, none of which the render
@@ -328,6 +353,9 @@ rt_ctx* rt_group_strip(rt_group* g, int i);
 int rt_group_last_hip_error(rt_group* g);
 /* rt_enable_pipelining on every strip (each on a stream of its own). */
 int rt_group_enable_pipelining(rt_group* g, int on);
+/* rt_set_phong_gbuffer on every strip; kept, as pipelining is, when rt_group_set_bounds,
+ * rt_group_set_plan or rt_group_balance re-create the contexts. */
+int rt_group_set_phong_gbuffer(rt_group* g, int on);
 /* Assemble frames into a caller-owned device buffer of H*W float4 on devices[0] (NULL: the
  * group's own).  Waits for the frames in flight first. */
 int rt_group_bind_frame(rt_group* g, void* device_ptr);

@@ -60,6 +60,8 @@ SIGNATURES = {
     "rt_compute_frames": (C.c_int, [_ctx, _fp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int]),
     "rt_set_frame_batch": (C.c_int, [_ctx, C.c_int]),
     "rt_set_tile_schedule": (C.c_int, [_ctx, C.c_int]),
+    "rt_set_phong_gbuffer": (C.c_int, [_ctx, C.c_int]),
+    "rt_phong_gbuffer": (C.c_int, [_ctx]),
     "rt_tile_schedule_state": (C.c_int, [_ctx]),
     "rt_tile_schedule_orders": (C.c_int, [_ctx]),
     "rt_set_cull_cache": (C.c_int, [_ctx, C.c_int]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "rt_group_strip": (_ctx, [_grp, C.c_int]),
     "rt_group_last_hip_error": (C.c_int, [_grp]),
     "rt_group_enable_pipelining": (C.c_int, [_grp, C.c_int]),
+    "rt_group_set_phong_gbuffer": (C.c_int, [_grp, C.c_int]),
     "rt_group_bind_frame": (C.c_int, [_grp, _vp]),
     "rt_group_frame_device_ptr": (_vp, [_grp]),
     "rt_group_upload_header": (C.c_int, [_grp, _vp, C.c_size_t]),

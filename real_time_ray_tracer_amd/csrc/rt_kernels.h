@@ -54,6 +54,8 @@ struct FrameParams {
   const float4* sph;         // [S] sphere-only geometry: geo for spheres, NaN for every other shape
   const float4* planes;      // [nplanes][2]: (normal, bits(index)), (p0, 0) of the planes among [0, nobj)
   int nplanes;               // set by the host (rt_shim) from the header's shape ids
+  int phong_gbuf;            // modes 3/4: launch the instantiations that also write nrm / dep (rt_set_phong_gbuffer);
+                             // read by the launcher only, in the padding behind nplanes, so no other member moves
   // AO bounce-ray cluster culling (set by the host, rt_shim build_clusters; ncl = 0: off):
   const float4* clus;        // [ncl] (centre, R): every member sphere lies within R of the centre
   const unsigned long long* clmask;  // [1 + kMaxClusters][kClusterWords]: always-tested spheres, then members
@@ -102,6 +104,8 @@ struct FrameParams {
 };
 static_assert(offsetof(FrameParams, bg) == 160 && offsetof(FrameParams, cull_frames) == 156,
               "cull_frames fills the padding in front of bg");
+static_assert(offsetof(FrameParams, phong_gbuf) == 204 && offsetof(FrameParams, clus) == 208,
+              "phong_gbuf fills the padding behind nplanes");
 
 // bytes of the sort frames in front of a cull table of `pools` pools (two float4 per pool)
 constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2 * sizeof(float4); }

@@ -4,6 +4,8 @@
 //
 //   phong_kernel     <- resources/p_compute.glsl   (mode 3)
 //   hybrid_kernel    <- resources/h_compute.glsl   (mode 4)
+//   phong_gbuf_kernel, hybrid_gbuf_kernel: the same two, also storing the primary hit's normal and
+//                       depth as the AO shaders do (rt_set_phong_gbuffer; the reference has no such shader)
 //   ao_batch_kernel  <- resources/ao_compute.glsl  (mode 2) / aop_compute.glsl (mode 1 pass 1)
 //   post_kernel      <- resources/aop_postprocessing.glsl (mode 1 pass 2)
 //
@@ -212,6 +214,28 @@ __device__ __forceinline__ FrameDst frame_dst(const FrameParams& P, int j) {
   const float4 L = P.mf_light[j];
   return FrameDst{mk(L.x, L.y, L.z), (float4*)P.hist_pix[(P.mf_slot0 + j) % P.F], j == P.mf_n - 1 ? P.image : nullptr};
 }
+// The g-buffer slot a Phong/hybrid frame writes with rt_set_phong_gbuffer on (include/rt/abi.h
+// "Phong g-buffer"; the GB instantiations only): the launch's slot, or frame j's of a batch.
+struct GbDst {
+  float4* nrm;
+  float4* dep;
+};
+template <bool MF>
+__device__ __forceinline__ GbDst frame_gb(const FrameParams& P, int j) {
+  if (!MF || P.mf_n <= 0) return GbDst{P.nrm, P.dep};
+  const int slot = (P.mf_slot0 + j) % P.F;
+  return GbDst{(float4*)P.hist_nrm[slot], (float4*)P.hist_dep[slot]};
+}
+// The primary hit as the kernel found it: (n, 1) and (t, 0, 0, 1), or zeros for a miss; the colour
+// store's lane-to-pixel map (store_color), the AO pass's plane layouts.  Plain stores, as the AO
+// pass's: they keep the lines in the XCD's L2 for a post-process pass that may read them next.
+__device__ __forceinline__ void store_gbuf(const FrameParams& P, const GbDst& gb, int x, int y, bool hit, f3 n, float t) {
+  const size_t off = (size_t)(y - P.band_row0) * P.W + x;
+  const float f = hit ? 1.0f : 0.0f;
+  nrm_store(gb.nrm, dep_plane(P), off, hit ? make_float4(n.x, n.y, n.z, f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  dep_store(gb.dep, dep_plane(P), off, make_float4(hit ? t : 0.0f, 0.0f, 0.0f, f));
+}
+
 // Multi-frame launches of modes 3/4 (FrameParams::mf_n frames): each block renders its tile in
 // frames blockIdx.z * FPB ... (up to FPB of them, one after another), so a launch dispatches FPB x
 // fewer workgroups and stages its LDS tables once per tile, not once per frame.  Every frame's
@@ -657,10 +681,11 @@ __device__ __forceinline__ bool shadow_lit_sph(const FrameParams& P, const float
 // their shadow rays are cone-culled, and PL adds the scene's planes (plane table, tested after
 // the spheres).  !ALLSPH (A/B builds only): the whole shape table staged in LDS, every shape
 // tested through eval_ray's id dispatch, no culling.
-template <bool ALLSPH, bool PL, bool LT, int BWX = 2, int BWY = 2>
+// GB: the pixel's primary hit goes to the g-buffer slot *gb as well (store_gbuf).
+template <bool ALLSPH, bool PL, bool LT, int BWX = 2, int BWY = 2, bool GB = false>
 __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* lds, int bx, int by, const FrameDst& fd,
                                            const float4* __restrict__ gsph, const float4* __restrict__ gshp,
-                                           const float4* pre0 = nullptr) {
+                                           const float4* pre0 = nullptr, const GbDst* gb = nullptr) {
   const int n = P.nobj;
   const float4* tab = (ALLSPH && !LT) ? gshp : lds;                       // geo | geo2 | col
   const float4* geo = (ALLSPH && !LT) ? gsph : (ALLSPH ? lds + 4 * n : lds);  // what the sphere tests read
@@ -687,11 +712,13 @@ __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* l
   float r, g, b;
   if (ind == -1) {
     r = P.bg.x; g = P.bg.y; b = P.bg.z;
+    if (GB) store_gbuf(P, *gb, x, y, false, mk(0.0f, 0.0f, 0.0f), 0.0f);
   } else {
     f3 curr = cam + t * dir;
     bool lit = ALLSPH ? lit_w : shadow_lit<ALLSPH>(geo, geo2, n, light, curr);
     int id = (ALLSPH && !PL) ? SHAPE_SPHERE : __float_as_int(geo2[ind].w);
     f3 nn = shape_normal(tab[ind], id, curr);
+    if (GB) store_gbuf(P, *gb, x, y, true, nn, t);
     float4 c = col[ind];
     if (lit) {
       f3 l = normalize(light - curr);
@@ -743,6 +770,28 @@ __global__ __launch_bounds__(kBlock) void phong_kernel(const float4* __restrict_
 #pragma unroll 1
   for (int j = 0; j < nj; ++j)
     phong_tile<ALLSPH, PL, LT>(P, lds, blockIdx.x, blockIdx.y, frame_dst(P, j0 + j), gsph, gshp);
+}
+
+// phong_kernel<true, PL, false, MF> that also writes the frame's normals and depth (the GB tile).
+// An entry point of its own, so that phong_kernel's instantiations keep their names and code.
+template <bool PL, bool MF>
+__global__ __launch_bounds__(kBlock) void phong_gbuf_kernel(const float4* __restrict__ gsph, const float4* __restrict__ gshp,
+                                                            FrameParams P) {
+  if constexpr (!MF) {
+    const float4 g0 = gsph[threadIdx.x & 63];  // as phong_kernel
+    const GbDst gb = frame_gb<false>(P, 0);
+    phong_tile<true, PL, false, 2, 2, true>(P, nullptr, blockIdx.x, blockIdx.y, frame_dst<false>(P, 0), gsph, gshp, &g0,
+                                            &gb);
+    return;
+  }
+  int j0;
+  const int nj = block_frames<kPhongFramesPerBlock>(P, j0);
+#pragma unroll 1
+  for (int j = 0; j < nj; ++j) {
+    const GbDst gb = frame_gb<true>(P, j0 + j);
+    phong_tile<true, PL, false, 2, 2, true>(P, nullptr, blockIdx.x, blockIdx.y, frame_dst(P, j0 + j), gsph, gshp, nullptr,
+                                            &gb);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -825,10 +874,13 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
 
 // ABL (A/B builds only, timing ablations): 1 = no shadow rays, 2 = no scene tests at all,
 // 3 = primary cull only, 5 = no bounce segments, 6 = bounces without the split rounds
-template <bool ALLSPH, bool PL, bool LT, int ABL = 0, int BWX = 2, int BWY = 2>
+// GB: segment 0's hit goes to the g-buffer slot *gb as well (store_gbuf), there and then, so that
+// neither t0 nor the normal stays live across the bounce rounds.
+template <bool ALLSPH, bool PL, bool LT, int ABL = 0, int BWX = 2, int BWY = 2, bool GB = false>
 __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* lds, int* perm, int bx, int by,
                                             const FrameDst& fd, const float4* __restrict__ gsph,
-                                            const float4* __restrict__ gshp, const float4* pre0 = nullptr) {
+                                            const float4* __restrict__ gshp, const float4* pre0 = nullptr,
+                                            const GbDst* gb = nullptr) {
   const int n = P.nobj;  // !ALLSPH or LT: LDS tables (see phong_kernel)
   const float4* tab = (ALLSPH && !LT) ? gshp : lds;
   const float4* geo = (ALLSPH && !LT) ? gsph : (ALLSPH ? lds + 4 * n : lds);
@@ -855,12 +907,14 @@ __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* 
     if (ind == -1) {
       ar = P.bg.x; ag = P.bg.y; ab = P.bg.z;
       stop = true;
+      if (GB && seg == 0 && active) store_gbuf(P, *gb, x, y, false, mk(0.0f, 0.0f, 0.0f), 0.0f);
     } else {
       // (ABL 9, timing ablation with ABL 5's single segment: the shading without its table loads)
       float4 att = ABL == 9 ? make_float4(0.5f, 0.5f, 0.5f, 0.0f) : col[ind];
       f3 curr = pos + t * dir;
       int id = (ALLSPH && !PL) ? SHAPE_SPHERE : __float_as_int(geo2[ind].w);
       f3 nn = ABL == 9 ? normalize(curr) : shape_normal(tab[ind], id, curr);
+      if (GB && seg == 0 && active) store_gbuf(P, *gb, x, y, true, nn, t);
       if (lit) {
         f3 l = normalize(light - curr);
         float spec = pow500(gclamp(dot(normalize(l - dir), nn), 0.0f, 1.0f));
@@ -986,6 +1040,28 @@ __global__ __launch_bounds__(64 * BWX * BWY) void hybrid_kernel(const unsigned* 
       hybrid_tile<ALLSPH, PL, LT, ABL, BWX, BWY>(P, lds, hperm + 64 * (threadIdx.x >> 6), blockIdx.x, blockIdx.y,
                                                  frame_dst(P, j0 + j), gsph, gshp);
   }
+}
+
+// hybrid_kernel<true, PL, false, 0, kHyBW, kHyBW, MF> that also writes the frame's normals and depth
+// (the GB tile); an entry point of its own, as phong_gbuf_kernel is.
+template <bool PL, int BWX, int BWY, bool MF>
+__global__ __launch_bounds__(64 * BWX * BWY) void hybrid_gbuf_kernel(const unsigned* __restrict__ tord,
+                                                                     const float4* __restrict__ gsph,
+                                                                     const float4* __restrict__ gshp, unsigned gx,
+                                                                     FrameParams P) {
+  static_assert(kHybridFramesPerBlock == 1, "one frame per block (hybrid_kernel's loop-free form)");
+  __shared__ int hperm[64 * BWX * BWY];
+  float4 g0;
+  if (!MF) g0 = gsph[threadIdx.x & 63];  // as hybrid_kernel
+  unsigned bx = blockIdx.x, by = blockIdx.y;
+  if (tord) {
+    const unsigned t = tord[blockIdx.x + blockIdx.y * gx];
+    bx = t & 0xffffu;
+    by = t >> 16;
+  }
+  const GbDst gb = frame_gb<MF>(P, blockIdx.z);
+  hybrid_tile<true, PL, false, 0, BWX, BWY, true>(P, nullptr, hperm + 64 * (threadIdx.x >> 6), bx, by,
+                                                  frame_dst<MF>(P, blockIdx.z), gsph, gshp, MF ? nullptr : &g0, &gb);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2951,6 +3027,20 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
   // survivor tests, vector loads for the hit's material), not staged in LDS per block (the LT
   // instantiations, A/B tools library only)
   const bool mf = p.mf_n > 0;  // multi-frame launch; single-frame ones take the MF = false kernels
+  if (p.phong_gbuf && (program == K_PHONG || program == K_HYBRID)) {  // rt_set_phong_gbuffer: the GB instantiations
+    if (program == K_PHONG) {
+      if (pl && mf) hipLaunchKernelGGL((phong_gbuf_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (pl) hipLaunchKernelGGL((phong_gbuf_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (mf) hipLaunchKernelGGL((phong_gbuf_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else hipLaunchKernelGGL((phong_gbuf_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+    } else {
+      if (pl && mf) hipLaunchKernelGGL((hybrid_gbuf_kernel<true, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (pl) hipLaunchKernelGGL((hybrid_gbuf_kernel<true, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (mf) hipLaunchKernelGGL((hybrid_gbuf_kernel<false, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else hipLaunchKernelGGL((hybrid_gbuf_kernel<false, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+    }
+    return hipGetLastError();
+  }
   switch (program) {
     case K_PHONG:
       if (pl && mf) hipLaunchKernelGGL((phong_kernel<true, true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);

@@ -185,6 +185,7 @@ struct rt_ctx {
   int batch_last = -1;         // the d_batch slot d_shapes points into after rt_compute_frames (else -1)
   TileSched sched[kSchedKinds];  // longest-first schedules (set up by the first launch of each kind)
   bool sched_on = true;          // rt_set_tile_schedule
+  bool phong_gbuf = false;       // rt_set_phong_gbuffer: modes 3/4 write normals and depth, over the band
   CullCache cull;                // the AO pools' primary-ray cull masks while camera and scene hold
   float4* d_mf_rb = nullptr;   // rt_compute_frames, mode 2: the rand_buffers of a multi-frame launch
   std::vector<float4> batch_host;
@@ -735,6 +736,11 @@ int run_program(rt_ctx* c, int program, int frame) {
       // pixels of the strip rows only; the halo rows' pixels are never read
       p.trace_row0 = c->own0;
       p.trace_rows = c->own_rows;
+      if (c->phong_gbuf) {  // a g-buffer writer like the AO programs below: the band, into the slot's buffers
+        p.trace_row0 = c->band0;
+        p.trace_rows = c->band_rows;
+        p.phong_gbuf = 1;
+      }
       p.out_pix = c->pix[c->pix_slot[frame]];
       return launch_sched(c, program, p, c->stream);
     case RT_PROG_AO_COMPUTE:
@@ -777,8 +783,10 @@ int run_program_mf(rt_ctx* c, int program, int slot0, int m, const float4* light
   rt::FrameParams p;
   fill_params(c, slot0, p);
   const bool ao = program == RT_PROG_AO_COMPUTE;
-  p.trace_row0 = ao ? c->band0 : c->own0;  // g-buffer writers trace the halo rows too (run_program)
-  p.trace_rows = ao ? c->band_rows : c->own_rows;
+  const bool gb = ao || c->phong_gbuf;
+  p.trace_row0 = gb ? c->band0 : c->own0;  // g-buffer writers trace the halo rows too (run_program)
+  p.trace_rows = gb ? c->band_rows : c->own_rows;
+  p.phong_gbuf = !ao && c->phong_gbuf;  // frame j: hist_nrm / hist_dep of its slot, next to hist_pix
   p.out_pix = c->pix[c->pix_slot[slot0]];
   p.mf_n = m;
   p.mf_slot0 = slot0;
@@ -1498,6 +1506,22 @@ int rt_set_tile_schedule(rt_ctx* c, int on) {
   c->sched_on = on != 0;
   return RT_OK;
 }
+
+int rt_set_phong_gbuffer(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  if (c->phong_gbuf == (on != 0)) return RT_OK;
+  if (c->band0 != c->own0 || c->band_rows != c->own_rows) {
+    // a strip's mode-4 launches change their rows, so their tiles: the schedule's costs and order
+    // restart, as on rt_set_tile_schedule (no launch in flight reads the tables freed here)
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    for (auto& h : c->sched) free_sched(h);
+  }
+  c->phong_gbuf = on != 0;
+  return RT_OK;
+}
+
+int rt_phong_gbuffer(rt_ctx* c) { return c ? (c->phong_gbuf ? 1 : 0) : RT_E_INVAL; }
 
 int rt_tile_schedule_state(rt_ctx* c) {
   if (!c) return RT_E_INVAL;

@@ -269,6 +269,17 @@ class Renderer:
         """Mode 4's longest-first tile order (rt_set_tile_schedule; on by default)."""
         self._c(self._lib.rt_set_tile_schedule(self.ctx, int(bool(on))), "rt_set_tile_schedule")
 
+    def set_phong_gbuffer(self, on: bool):
+        """Modes 3 and 4 also store the primary hit's normal and depth in the frame's ring slot, as
+        the AO modes do, and trace a strip's halo rows for them (rt_set_phong_gbuffer; off by
+        default, as in the reference).  The colours do not depend on it."""
+        self._c(self._lib.rt_set_phong_gbuffer(self.ctx, int(bool(on))), "rt_set_phong_gbuffer")
+
+    @property
+    def phong_gbuffer(self) -> bool:
+        """Whether modes 3 and 4 write normals and depth (rt_phong_gbuffer)."""
+        return bool(self._c(self._lib.rt_phong_gbuffer(self.ctx), "rt_phong_gbuffer"))
+
     def tile_schedule_state(self) -> int:
         """0 off, 1 on (row order so far), 2 a longest-first order in use (rt_tile_schedule_state)."""
         return self._c(self._lib.rt_tile_schedule_state(self.ctx), "rt_tile_schedule_state")
@@ -541,6 +552,11 @@ class StripGroup:
 
     def enable_pipelining(self, on: bool = True):
         self._c(self._lib.rt_group_enable_pipelining(self.g, int(bool(on))), "rt_group_enable_pipelining")
+
+    def set_phong_gbuffer(self, on: bool):
+        """Renderer.set_phong_gbuffer on every strip (rt_group_set_phong_gbuffer); kept when the
+        strips are re-created by set_bounds, set_plan or balance."""
+        self._c(self._lib.rt_group_set_phong_gbuffer(self.g, int(bool(on))), "rt_group_set_phong_gbuffer")
 
     def bind_frame(self, device_ptr: int | None):
         self._c(self._lib.rt_group_bind_frame(self.g, C.c_void_p(device_ptr) if device_ptr else None),
