@@ -38,17 +38,21 @@ $(OBJDIR)/rt_kernels.o: $(CSRC)/rt_kernels.hip $(CSRC)/*.h include/rt/*.h | $(OB
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(OBJDIR)/rt_host.o: $(CSRC)/rt_host.cpp include/rt/*.h | $(OBJDIR)
+# the host-only units (no HIP header): rt_host.cpp, rt_plan.cpp
+$(OBJDIR)/rt_host.o $(OBJDIR)/rt_plan.o: $(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -c $< -o $@
 
 $(OBJDIR)/rt_group.o: $(CSRC)/rt_group.cpp $(CSRC)/rt_kernels.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Iinclude -c $< -o $@
 
+# the shim and its components (rt_stage, rt_sched, rt_cull, rt_gbuf, rt_timing), the host-only units, the group
+SHIM_OBJS := $(addprefix $(OBJDIR)/,rt_shim.o rt_stage.o rt_sched.o rt_cull.o rt_gbuf.o rt_timing.o rt_host.o rt_plan.o rt_group.o)
+
 # BUILD_INFO: sha1 of the library's sources (+ the git commit they were built at, "+dirty" if
 # they differ from it), so measurements can name the kernel code they were taken on
-$(LIB): $(OBJDIR)/rt_kernels.o $(OBJDIR)/rt_shim.o $(OBJDIR)/rt_host.o $(OBJDIR)/rt_group.o
+$(LIB): $(OBJDIR)/rt_kernels.o $(SHIM_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
-	@src=$$(cat $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/rt_host.cpp $(CSRC)/rt_group.cpp include/rt/*.h Makefile | sha1sum | cut -c1-12); \
+	@src=$$(cat $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.cpp include/rt/*.h Makefile | sha1sum | cut -c1-12); \
 	 commit=$$(git rev-parse --short=12 HEAD 2>/dev/null || echo unknown); \
 	 git diff --quiet HEAD -- $(CSRC) include Makefile 2>/dev/null || commit="$$commit+dirty"; \
 	 printf '{"src_sha1": "%s", "commit": "%s"}\n' "$$src" "$$commit" > $(dir $@)BUILD_INFO
@@ -57,7 +61,7 @@ ABLIB := build/librtrt_ab.so
 $(OBJDIR)/rt_kernels_ab.o: tools/ab/rt_kernels_ab.hip $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(KARG_PRELOAD) -I$(CSRC) -x hip -c $< -o $@
 
-$(ABLIB): $(OBJDIR)/rt_kernels_ab.o $(OBJDIR)/rt_shim.o $(OBJDIR)/rt_host.o $(OBJDIR)/rt_group.o
+$(ABLIB): $(OBJDIR)/rt_kernels_ab.o $(SHIM_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 ablib: $(ABLIB)

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rt_table.h"
+
 // Normals slot layout, shared by the kernels and the shim (rt_download_rect reads the slots
 // directly): 1 = an xyz plane then a w plane (production), 0 = interleaved float4 (the round-2
 // layout, A/B builds only; set it for both translation units or neither).
@@ -12,7 +14,7 @@
 namespace rt {
 
 constexpr int kMaxFrames = 16;
-constexpr int kMaxBatch = 32;  // frames per multi-frame Phong/hybrid launch
+// (kMaxBatch, the frames per multi-frame launch, and the device table layout: rt_table.h)
 // Hybrid (mode 4) workgroups of kHyBW x kHyBW waves, each wave an 8x8 pixel tile; the tile
 // schedule's units are these workgroups (rt_shim launch_sched).  2x2 (16x16 pixels, 4 waves).
 // Round 5 A/Bs at (b), tables read through the caches: in row order 1x1 33.1, 2x1 33.6, 2x2 34.2,
@@ -88,7 +90,7 @@ struct FrameParams {
   // multi-frame AO launch (mode 2, gridDim.y = mf_n): frame j reads rand_buffer mf_rb[j * 2 spp ..]
   // and writes slot (mf_slot0 + j) % F (hist_pix / hist_nrm / hist_dep); the image by frame mf_n - 1
   const float4* mf_rb;
-  // hybrid (mode 4) tile schedule (rt_shim hy_schedule): block (x, y) renders the 16x16 tile
+  // hybrid (mode 4) tile schedule (rt_sched.h TileSched): block (x, y) renders the 16x16 tile
   // tile_order[x + y * gridDim.x] (packed x | y << 16) when non-null, else tile (x, y); each wave
   // stores its bounce-round count at tile_cost[tile * 4 + wave] when non-null
   const unsigned* tile_order;
@@ -109,38 +111,6 @@ static_assert(offsetof(FrameParams, phong_gbuf) == 204 && offsetof(FrameParams, 
 
 // bytes of the sort frames in front of a cull table of `pools` pools (two float4 per pool)
 constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2 * sizeof(float4); }
-
-// AO pools: kAoPool samples each, i.e. max(1, kAoPool / spp) consecutive pixels of the launch's rows
-constexpr int kAoPool = 256;
-constexpr long long ao_pool_count(int trace_rows, int W, int spp) {
-  const int TP = kAoPool / spp > 0 ? kAoPool / spp : 1;
-  return ((long long)trace_rows * W + TP - 1) / TP;
-}
-
-// Bounce-ray cluster culling (AO later bounce rounds): at most kMaxClusters clusters (a wave-uniform
-// u64 of kept clusters), member masks over the first kClusterWords * 64 spheres.
-constexpr int kMaxClusters = 64;
-constexpr int kClusterWords = 4;
-
-// Device shape table of one header copy, in float4 units from its base (rt_shim fills it):
-//   [0, 4S)          geo, geo2, col, aux        (rt_device.h "scene tables")
-//   [4S, 5S)         sph: geo of spheres, NaN of other shapes (never accepted by sphere_candidate)
-//   [5S, 7S)         planes: 2 float4 per plane, compacted, ascending index
-//   [7S, 7S + 64)    clusters: (centre, R) per cluster
-//   then (1 + 64) * 4 u64 cluster masks (the always-tested spheres, then each cluster's members)
-//   then [S) camrel: per sphere (camera - centre, dot of it with itself), NaN for other shapes:
-//        the camera rays' sphere tests without the per-lane subtraction and self dot (phong /
-//        hybrid primary rays; the same float operations, done once per frame on the host)
-//   then rand_buffer[2 spp]
-__host__ __device__ constexpr size_t sphere_table(int S) { return (size_t)4 * S; }
-__host__ __device__ constexpr size_t plane_table(int S) { return (size_t)5 * S; }
-__host__ __device__ constexpr size_t cluster_table(int S) { return (size_t)7 * S; }
-__host__ __device__ constexpr size_t cluster_mask_table(int S) { return cluster_table(S) + kMaxClusters; }
-__host__ __device__ constexpr size_t camrel_table(int S) {
-  return cluster_mask_table(S) + (size_t)(1 + kMaxClusters) * kClusterWords / 2;
-}
-__host__ __device__ constexpr size_t rand_table(int S) { return camrel_table(S) + (size_t)S; }
-__host__ __device__ constexpr size_t table_vec4(int S, int spp) { return rand_table(S) + (size_t)2 * spp; }
 
 enum KernelId { K_AOP = 1, K_POST = 2, K_AO = 3, K_PHONG = 4, K_HYBRID = 5 };
 

@@ -1,4 +1,4 @@
-"""The AO cull cache (rt_set_cull_cache, rt_shim CullCache): while camera and scene hold, the pools
+"""The AO cull cache (rt_set_cull_cache, rt_cull.h CullCache): while camera and scene hold, the pools
 of an AO launch load their primary-ray cull masks from a table instead of computing them.  The
 reference in every case is the same library with the cache off on a second context fed the same
 headers; images, pixels, normals and depth must be equal bit for bit, and with the counters on the

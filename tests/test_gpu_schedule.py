@@ -1,4 +1,4 @@
-"""Mode 4's longest-first tile schedule (rt_set_tile_schedule, rt_shim HySched): the workgroups
+"""Mode 4's longest-first tile schedule (rt_set_tile_schedule, rt_sched.h TileSched): the workgroups
 of h_compute's dispatch (src/main.cpp:604, resources/h_compute.glsl) run their 16x16 tiles in the
 order of the bounce rounds recent frames needed.  Only the order changes: the frames rendered
 with the schedule in use equal those rendered in row order bit for bit, and the last one equals

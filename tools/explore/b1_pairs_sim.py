@@ -120,7 +120,7 @@ def batch_masks(P, Dn, L, geo):
 
 
 def build_clusters(geo, size):
-    """rt_shim.hip build_clusters: recursive median splits of the centres along the widest axis
+    """rt_plan.cpp build_clusters: recursive median splits of the centres along the widest axis
     into groups of <= size; (centre, R) with every member inside (float64 here)."""
     idx = list(range(geo.shape[0]))
     work, groups = [(0, len(idx))], []
