@@ -233,6 +233,71 @@ void* rt_image_device_ptr(rt_ctx* ctx);
 /* Render the image into a caller-owned device buffer of R*W float4 (NULL = own buffer). */
 int rt_bind_image(rt_ctx* ctx, void* device_ptr);
 
+/* ---- ray queries: closest hit, occlusion, pixel picks ----------------------------------- */
+/* What does this ray hit?  The frame kernels' closest-hit scan and shadow test for the caller's own
+ * rays (the reference's mouseCallback is an empty stub, src/main.cpp:286-296).
+ * The scene in effect is the header last given to the context, by rt_upload_header,
+ * rt_compute_frames or the host-buffer calls; nobj = int(mode.z).  Before any header: RT_E_STATE.
+ * A strip context answers exactly as a whole-frame context does (scene and camera are the whole
+ * frame's); no g-buffer, image or counter is touched.
+ *   Closest hit of ray (o, d) at threshold thr, the reference's loop (p_compute.glsl:177-188,
+ *   h_compute.glsl:199-210, ao_compute.glsl:183-194) with the threshold as a parameter:
+ *     t = -1, ind = -1;  for i = 0 .. nobj-1 ascending:  res = eval_ray(o, d, i)
+ *       (sphere_eval_ray for a sphere, plane_eval_ray for a plane, -1 for anything else: a
+ *       rectangle is never hit);  if (res > thr && (res < t || t < 0)) { t = res; ind = i; }
+ *   so the lowest index wins a tie.  d is used as given, NOT normalised (the sphere test assumes a
+ *   unit vector, as the reference's does).  Per ray: t (float, -1 for a miss), ind (int32, -1 for a
+ *   miss), normal (3 floats): zeros for a miss, the stored normal for a plane, for a sphere
+ *   normalize((o + t*d) - c) with the hit point formed as one multiply and one add per component in
+ *   binary32 without contraction: the value the Phong g-buffer stores for the camera's rays.  NaN
+ *   and infinite operands follow the arithmetic (the sign and payload of a NaN result are not
+ *   specified); a NaN res is never accepted.  thr must be finite and >= 0 (else RT_E_INVAL).
+ *   Pixel rays: for integers (x, y) in frame coordinates (row 0 = the bottom row; any int32, also
+ *   outside the frame) o = camera_location, d = normalize(llc_minus_campos + (x/W)*horizontal +
+ *   (y/H)*vertical) (p_compute.glsl:233-235, x/W and y/H correctly rounded binary32 quotients), the
+ *   ray the frame kernels trace for that pixel.  At thr = 0 the answer is what a mode-3 Phong
+ *   g-buffer frame stores for the pixel, at 0.001 mode 4's, at 0.0001 the AO programs' first segment.
+ *   Occlusion of the segment from a to b is shadow_ray(pos = a, light = b) (p_compute.glsl:145-166):
+ *   l = normalize(b - a), len = length(b - a), o = a + 0.01f*l; occluded iff some i < nobj has
+ *   t = eval_ray(o, l, i), taken as binary64, with t > 0.0001f and length(dvec3(t*l)) < len.  One
+ *   byte per segment, 1 or 0.  a == b makes l NaN, and nothing occludes.
+ * All float semantics as oracle/rt_oracle.h states them. */
+#define RT_QUERY_MAX_RAYS ((size_t)1 << 28)
+/* Host pointers; the call returns when the answers are there (it waits like rt_download).  Any
+ * output pointer may be NULL; n == 0 is RT_OK.  origins / dirs / normals / from / to: [n][3] floats,
+ * xy: [n][2] int32, t: [n] floats, ind: [n] int32, out: [n] bytes; rt_trace_pixels' dirs receives the
+ * rays used.  RT_E_INVAL for a NULL context, a NULL input with n > 0, n > RT_QUERY_MAX_RAYS or a bad
+ * thr.  The rays are staged through a device workspace of the context's own, allocated by the first
+ * such call, replaced when a call needs more, freed by rt_destroy: no allocation per call. */
+int rt_trace_rays(rt_ctx* ctx, const float* origins, const float* dirs, size_t n, float thr, float* t, int32_t* ind,
+                  float* normals);
+int rt_trace_pixels(rt_ctx* ctx, const int32_t* xy, size_t n, float thr, float* t, int32_t* ind, float* normals,
+                    float* dirs);
+int rt_occluded(rt_ctx* ctx, const float* from, const float* to, size_t n, uint8_t* out);
+/* The same with device pointers (same layouts) on the context's device: the kernel is enqueued on
+ * rt_get_stream(ctx) behind everything the context has enqueued so far (a pipelined sequence is
+ * joined first), and the call returns without waiting: no allocation, no host wait, no event or
+ * stream created.  A later header upload or launch is ordered after the query. */
+int rt_trace_rays_device(rt_ctx* ctx, const void* d_origins, const void* d_dirs, size_t n, float thr, void* d_t,
+                         void* d_ind, void* d_normals);
+int rt_trace_pixels_device(rt_ctx* ctx, const void* d_xy, size_t n, float thr, void* d_t, void* d_ind,
+                           void* d_normals, void* d_dirs);
+int rt_occluded_device(rt_ctx* ctx, const void* d_from, const void* d_to, size_t n, void* d_out);
+/* Diagnostic, like rt_cull_cache_stats: bytes of the host-pointer calls' device workspace, 0 until
+ * the first of them and unchanged by a call that fits (what "no allocation per call" means; the
+ * tests hold the calls to it).  Nothing else depends on it. */
+size_t rt_query_workspace_bytes(rt_ctx* ctx);
+/* Host only: the same rules in C on a header of rt_header_bytes(cfg->num_shapes, cfg->spp) bytes,
+ * the specification of the six above; they never touch the GPU.  rt_pixel_rays_host writes the pixel
+ * rays themselves (it reads cfg->width and cfg->height).  RT_E_INVAL as above, and for a header of
+ * another size or an int(mode.z) outside [0, num_shapes]. */
+int rt_trace_rays_host(const rt_config* cfg, const void* header, size_t header_bytes, const float* origins,
+                       const float* dirs, size_t n, float thr, float* t, int32_t* ind, float* normals);
+int rt_pixel_rays_host(const rt_config* cfg, const void* header, size_t header_bytes, const int32_t* xy, size_t n,
+                       float* origins, float* dirs);
+int rt_occluded_host(const rt_config* cfg, const void* header, size_t header_bytes, const float* from, const float* to,
+                     size_t n, uint8_t* out);
+
 /* ---- 8-bit display output (the blit, src/main.cpp:783-797) -------------------------- */
 /* The reference ends a frame by drawing the rgba32f image into an 8-bit framebuffer
  * (src/main.cpp:783-797 through resources/shader_fragment.glsl:9-19: colour unchanged, alpha 1).

@@ -36,6 +36,7 @@ class rt_config(C.Structure):
 
 
 _fp = C.POINTER(C.c_float)
+_ip = C.POINTER(C.c_int32)
 _vp = C.c_void_p
 _ctx = C.c_void_p
 _grp = C.c_void_p
@@ -75,6 +76,17 @@ SIGNATURES = {
     "rt_upload_gbuffer": (C.c_int, [_ctx, _fp, _fp, _fp]),
     "rt_image_device_ptr": (_vp, [_ctx]),
     "rt_bind_image": (C.c_int, [_ctx, _vp]),
+    "rt_trace_rays": (C.c_int, [_ctx, _fp, _fp, C.c_size_t, C.c_float, _fp, _ip, _fp]),
+    "rt_trace_pixels": (C.c_int, [_ctx, _ip, C.c_size_t, C.c_float, _fp, _ip, _fp, _fp]),
+    "rt_occluded": (C.c_int, [_ctx, _fp, _fp, C.c_size_t, _vp]),
+    "rt_trace_rays_device": (C.c_int, [_ctx, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp, _vp]),
+    "rt_trace_pixels_device": (C.c_int, [_ctx, _vp, C.c_size_t, C.c_float, _vp, _vp, _vp, _vp]),
+    "rt_occluded_device": (C.c_int, [_ctx, _vp, _vp, C.c_size_t, _vp]),
+    "rt_query_workspace_bytes": (C.c_size_t, [_ctx]),
+    "rt_trace_rays_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, _fp, C.c_size_t, C.c_float, _fp, _ip,
+                                     _fp]),
+    "rt_pixel_rays_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _ip, C.c_size_t, _fp, _fp]),
+    "rt_occluded_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, _fp, C.c_size_t, _vp]),
     "rt_present": (C.c_int, [_ctx, C.c_int]),
     "rt_present_device_ptr": (_vp, [_ctx]),
     "rt_bind_present": (C.c_int, [_ctx, _vp]),

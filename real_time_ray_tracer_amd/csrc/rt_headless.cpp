@@ -10,7 +10,9 @@
 //
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
 //               [--scene synthetic|1|5|6] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
-//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH]
+//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH] [--pick X,Y]
+// --pick X,Y prints, after the last frame, one line `pick x y ind t nx ny nz`: the closest hit of pixel
+// (X, Y)'s primary ray (frame coordinates, row 0 = the bottom row) by rt_trace_pixels at threshold 0.
 // --strips G > 1 renders the frame as G row strips through the rt_group_* entry points: strip i
 // on device devices[i % #devices] (default, without --devices: every visible device in turn,
 // starting at --device), cost-balanced with --balance ROUNDS timed plans (0: equal strips),
@@ -114,6 +116,8 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
 int main(int argc, char** argv) {
   int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0;
   int ppm_w = 0, ppm_h = 0;  // --ppm-size (0: the frame's own size)
+  bool pick = false;         // --pick X,Y: what is under that pixel after the last frame
+  int pick_x = 0, pick_y = 0;
   std::string scene = "1", ppm, devlist;
   unsigned long long seed = 1234;
   for (int i = 1; i + 1 < argc; i += 2) {
@@ -139,7 +143,18 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (k == "--pick") {
+      if (std::sscanf(v.c_str(), "%d,%d", &pick_x, &pick_y) != 2) {
+        std::fprintf(stderr, "rt_headless: --pick wants X,Y (frame coordinates, row 0 = the bottom row)\n");
+        return 2;
+      }
+      pick = true;
+    }
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
+  }
+  if (pick && strips > 1) {
+    std::fprintf(stderr, "rt_headless: --pick asks one context; it does not go with --strips\n");
+    return 2;
   }
   const float aspect = (W * 3 == H * 4) ? 1.333333f : 1.777777f;  // main.cpp:39-40
   int S = scene == "synthetic" ? N : 10;
@@ -186,6 +201,13 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> img((size_t)W * H * 4);
     check(rt_download_rgba8(ctx, 1, img.data()), "rt_download_rgba8");
     write_ppm(ppm.c_str(), img, W, H);
+  }
+  if (pick) {  // the closest hit of the pixel's primary ray as mode 3 shows it (t > 0): what mouseCallback would pick
+    const int32_t xy[2] = {pick_x, pick_y};
+    float t = 0.0f, nrm[3] = {0.0f, 0.0f, 0.0f};
+    int32_t ind = 0;
+    check(rt_trace_pixels(ctx, xy, 1, 0.0f, &t, &ind, nrm, nullptr), "rt_trace_pixels");
+    std::printf("pick %d %d %d %.9g %.9g %.9g %.9g\n", pick_x, pick_y, (int)ind, t, nrm[0], nrm[1], nrm[2]);
   }
   rt_destroy(ctx);
   return 0;

@@ -157,6 +157,40 @@ hipError_t launch_present(const float4* image, void* out, int W, int rows, int t
 hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, int out_w, int out_h, int top_down,
                                  hipStream_t stream);
 
+// Ray queries (include/rt/abi.h "Ray queries"): the scene and camera a query reads, as launch
+// arguments.  shapes: the base of a device table copy (rt_table.h).
+struct QueryScene {
+  const float4* shapes;
+  int S, nobj, nplanes;  // table stride, int(mode.z), planes among [0, nobj)
+  float fW, fH;          // (float)W, (float)H of the whole frame
+  float hx, hy, hz;      // horizontal
+  float vx, vy, vz;      // vertical
+  float lx, ly, lz;      // llc_minus_campos
+  float cx, cy, cz;      // camera_location
+};
+// Closest hit of n rays at threshold thr (finite, >= 0), one ray per lane: the rays (origins[i],
+// dirs[i]) ([n][3] each), or when xy is non-null the camera's rays through the pixels xy[i]
+// ([n][2] int).  Outputs, each skipped when null: t [n], ind [n], nrm [n][3], and for pixel rays
+// dir_out [n][3], the directions used.  All-sphere and with-planes instantiations, chosen from
+// sc.nplanes as launch_program chooses.  n <= 2^28 (hipErrorInvalidValue otherwise); n == 0 launches nothing.
+struct RayQuery {
+  QueryScene sc;
+  const float* origins;
+  const float* dirs;
+  const int* xy;
+  size_t n;
+  float thr;
+  float* t;
+  int* ind;
+  float* nrm;
+  float* dir_out;
+};
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream);
+// Occlusion of n segments from[i] -> to[i] ([n][3] each): out[i] = 1 when shadow_ray(pos = from[i],
+// light = to[i]) finds an occluder (p_compute.glsl:145-166), else 0.  Same instantiations and limits.
+hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
+                           hipStream_t stream);
+
 // Device math self-test (rt_selftest_math).
 hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream);
 

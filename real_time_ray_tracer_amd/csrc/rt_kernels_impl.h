@@ -42,7 +42,9 @@ __device__ __forceinline__ void stage_shapes(const FrameParams& P, float4* lds) 
   }
 }
 
-__device__ __forceinline__ f3 primary_dir(const FrameParams& P, float hp, float vp) {
+// P: anything with the camera's lx.. / hx.. / vx.. members (FrameParams, QueryScene)
+template <class Cam>
+__device__ __forceinline__ f3 primary_dir(const Cam& P, float hp, float vp) {
   // normalize(llc_minus_campos + hp*horizontal + vp*vertical), p_compute.glsl:235
   f3 a = mk(P.lx + hp * P.hx, P.ly + hp * P.hy, P.lz + hp * P.hz);
   return normalize(mk(a.x + vp * P.vx, a.y + vp * P.vy, a.z + vp * P.vz));
@@ -2966,6 +2968,154 @@ hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, i
   const int gy = out_h < per ? out_h : per;
   hipLaunchKernelGGL(present_scaled_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, stream, image, W, R,
                      (unsigned*)out, out_w, out_h, top_down, wide);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// ray queries — include/rt/abi.h "Ray queries" (rt_trace_rays / rt_trace_pixels / rt_occluded)
+// ---------------------------------------------------------------------------------------
+// One sphere of a query's closest-hit scan: sphere_eval_ray (p_compute.glsl:77-109) and the scan's
+// acceptance `res > thr && (res < t || t < 0)`, every case of the reference kept (thr is a runtime
+// value here and 0 the common one, so none of sphere_candidate's shortcuts, which lean on a literal
+// threshold, is taken): del == 0 gives -b, two negative roots give -1, and the square root is
+// sqrt_rn, equal to sqrtf on every input.  The tail sits behind a wave-uniform branch as in
+// sphere_candidate: when some lane's ray meets the sphere it runs on every active lane and
+// del >= 0 joins the acceptance (a negative or NaN discriminant: -1 / NaN in the reference, which
+// the scan never accepts).
+__device__ __forceinline__ void query_sphere(f3 pos, f3 dir, float4 g, int i, float thr, float& t, int& ind) {
+  const f3 pmc = pos - xyz(g);
+  const float b = dot(dir, pmc);
+  const float del = fmaf(g.w, g.w, fmaf(b, b, -dot(pmc, pmc)));
+  const bool meets = del >= 0.0f;
+  if (__builtin_amdgcn_ballot_w64(meets) != 0) {
+    const float s = sqrt_rn(del);
+    const float nb = -1.0f * b;
+    const float t1 = nb + s, t2 = nb - s;
+    float res = (t2 < 0.0f) ? ((t1 < 0.0f) ? -1.0f : t1) : t2;
+    res = (del == 0.0f) ? nb : res;
+    const bool acc = meets & (res > thr) & ((res < t) | (t < 0.0f));  // no short-circuit branches
+    t = acc ? res : t;
+    ind = acc ? i : ind;
+  }
+}
+
+// The closest-hit scan of a query ray, ascending index (the lowest index wins a tie).  PL = false:
+// no plane among the scene's shapes, so the sphere table is scanned (NaN rows for every other
+// shape: never accepted).  PL: eval_ray's dispatch on the shape id (p_compute.glsl:121-138), in
+// index order, so the scan's own tie rule holds between spheres and planes.  The shape index is
+// wave-uniform: the rows come through scalar loads and the id dispatch is a scalar branch.
+template <bool PL>
+__device__ __forceinline__ int query_closest(const QueryScene& sc, f3 pos, f3 dir, float thr, float& t_out) {
+  const float4* __restrict__ geo = sc.shapes;
+  const float4* __restrict__ geo2 = sc.shapes + sc.S;
+  const float4* __restrict__ sph = sc.shapes + sphere_table(sc.S);
+  float t = -1.0f;
+  int ind = -1;
+  int i = 0;
+  if (!PL)  // four rows per scalar load, the same ascending order (the next four are not requested ahead
+            // as closest_hit_pf does: each group waits for its load, hidden only by the other waves)
+    for (; i + 4 <= sc.nobj; i += 4) {
+      const float4 g0 = sph[i], g1 = sph[i + 1], g2 = sph[i + 2], g3 = sph[i + 3];
+      query_sphere(pos, dir, g0, i, thr, t, ind);
+      query_sphere(pos, dir, g1, i + 1, thr, t, ind);
+      query_sphere(pos, dir, g2, i + 2, thr, t, ind);
+      query_sphere(pos, dir, g3, i + 3, thr, t, ind);
+    }
+  for (; i < sc.nobj; ++i) {
+    if (!PL) {
+      query_sphere(pos, dir, sph[i], i, thr, t, ind);
+    } else {
+      const float4 g = geo[i], g2 = geo2[i];
+      const int id = __float_as_int(g2.w);
+      if (id == SHAPE_SPHERE) {
+        query_sphere(pos, dir, g, i, thr, t, ind);
+      } else if (id == SHAPE_PLANE) {
+        const float res = plane_eval(pos, dir, g, g2);
+        const bool acc = (res > thr) & ((res < t) | (t < 0.0f));
+        t = acc ? res : t;
+        ind = acc ? i : ind;
+      }
+    }
+  }
+  t_out = t;
+  return ind;
+}
+
+// One ray per lane.  PIX: the camera's ray through pixel xy[i], formed as the frame kernels form it
+// (primary_dir on x / W and y / H; the division is the IEEE one, whose value div_rn_by returns for
+// the frame kernels' in-frame coordinates, because a query's coordinates may be any int32).
+template <bool PL, bool PIX>
+__global__ __launch_bounds__(kBlock) void ray_query_kernel(RayQuery Q) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= Q.n) return;
+  f3 o, d;
+  if (PIX) {
+    const int x = Q.xy[2 * i], y = Q.xy[2 * i + 1];
+    o = mk(Q.sc.cx, Q.sc.cy, Q.sc.cz);
+    d = primary_dir(Q.sc, (float)x / Q.sc.fW, (float)y / Q.sc.fH);
+  } else {
+    o = mk(Q.origins[3 * i], Q.origins[3 * i + 1], Q.origins[3 * i + 2]);
+    d = mk(Q.dirs[3 * i], Q.dirs[3 * i + 1], Q.dirs[3 * i + 2]);
+  }
+  float t;
+  const int ind = query_closest<PL>(Q.sc, o, d, Q.thr, t);
+  if (Q.t) Q.t[i] = t;
+  if (Q.ind) Q.ind[i] = ind;
+  if (Q.nrm) {
+    f3 n = mk(0.0f, 0.0f, 0.0f);
+    if (ind >= 0) {  // the Phong g-buffer's normal (phong_tile): of shape ind at o + t * d
+      const int id = PL ? __float_as_int(Q.sc.shapes[Q.sc.S + ind].w) : SHAPE_SPHERE;
+      n = shape_normal(Q.sc.shapes[ind], id, o + t * d);
+    }
+    Q.nrm[3 * i] = n.x;
+    Q.nrm[3 * i + 1] = n.y;
+    Q.nrm[3 * i + 2] = n.z;
+  }
+  if (PIX && Q.dir_out) {
+    Q.dir_out[3 * i] = d.x;
+    Q.dir_out[3 * i + 1] = d.y;
+    Q.dir_out[3 * i + 2] = d.z;
+  }
+}
+
+// One segment per lane: shadow_ray (p_compute.glsl:145-166) from from[i] towards to[i]; out = !lit.
+template <bool PL>
+__global__ __launch_bounds__(kBlock) void occluded_kernel(QueryScene sc, const float* __restrict__ from,
+                                                          const float* __restrict__ to, size_t n,
+                                                          unsigned char* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const f3 a = mk(from[3 * i], from[3 * i + 1], from[3 * i + 2]);
+  const f3 b = mk(to[3 * i], to[3 * i + 1], to[3 * i + 2]);
+  const bool lit = PL ? shadow_lit<false>(sc.shapes, sc.shapes + sc.S, sc.nobj, b, a)
+                      : shadow_lit<true>(sc.shapes + sphere_table(sc.S), nullptr, sc.nobj, b, a);
+  out[i] = lit ? 0 : 1;
+}
+
+constexpr size_t kQueryMaxRays = (size_t)1 << 28;  // RT_QUERY_MAX_RAYS: the grid's x stays below 2^31
+
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream) {
+  if (q.n == 0) return hipSuccess;
+  if (q.n > kQueryMaxRays || !q.sc.shapes || (!q.xy && (!q.origins || !q.dirs))) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((q.n + kBlock - 1) / kBlock));
+  const bool pl = q.sc.nplanes > 0;
+  if (q.xy) {
+    if (pl) hipLaunchKernelGGL((ray_query_kernel<true, true>), grid, dim3(kBlock), 0, stream, q);
+    else hipLaunchKernelGGL((ray_query_kernel<false, true>), grid, dim3(kBlock), 0, stream, q);
+  } else {
+    if (pl) hipLaunchKernelGGL((ray_query_kernel<true, false>), grid, dim3(kBlock), 0, stream, q);
+    else hipLaunchKernelGGL((ray_query_kernel<false, false>), grid, dim3(kBlock), 0, stream, q);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
+                           hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > kQueryMaxRays || !sc.shapes || !from || !to || !out) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  if (sc.nplanes > 0) hipLaunchKernelGGL(occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  else hipLaunchKernelGGL(occluded_kernel<false>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   return hipGetLastError();
 }
 

@@ -22,7 +22,7 @@
 // are those of the sequential order, bit for bit.
 //
 // The subsystems are components with their own state, operations and release() (rt_stage.h,
-// rt_sched.h, rt_cull.h, rt_gbuf.h, rt_timing.h); the arithmetic that needs no HIP is rt_plan.cpp.
+// rt_sched.h, rt_cull.h, rt_gbuf.h, rt_timing.h, rt_query.h); the arithmetic that needs no HIP is rt_plan.cpp.
 // This file keeps the context, the launches and the entry points.
 #include <hip/hip_runtime.h>
 
@@ -38,6 +38,7 @@
 #include "rt_hip_util.h"
 #include "rt_kernels.h"
 #include "rt_plan.h"
+#include "rt_query.h"
 #include "rt_sched.h"
 #include "rt_stage.h"
 #include "rt_timing.h"
@@ -66,12 +67,16 @@ struct rt_ctx {
   float4* d_rb_buf[kAoStreams] = {};      // = d_shapes_buf[k] + rt::rand_table(S) (one allocation, one upload)
   float4* d_shapes = nullptr;  // the copy the next dispatch reads
   float4* d_rb = nullptr;
+  // the table of the header last given to the context, which a ray query reads: d_shapes, except that
+  // after a pipelined frame d_shapes moves on to the copy the next upload will fill
+  const float4* d_scene = nullptr;
   // the subsystems
   rt::StageRing stage;      // pinned staging buffers of the async uploads
   rt::TileSched sched;      // mode 4's longest-first tile schedule (set up by the first hybrid launch)
   rt::CullCache cull;       // the AO pools' primary-ray cull masks while camera and scene hold
   rt::GbufRing gbuf;        // pixels / normals / depth: F slots and pipe_depth more buffers each
   rt::LaunchTiming timing;  // rt_enable_timing
+  rt::QueryWork query;      // the host-pointer ray queries' device workspace (made by the first such query)
   // pipelined mode 1
   bool pipelined = false;
   hipStream_t out_stream = nullptr, own_out_stream = nullptr;
@@ -138,6 +143,7 @@ void free_all(rt_ctx* c) {
   c->stage.release();
   c->timing.release();
   c->gbuf.release();
+  c->query.release();
   if (c->d_image_own) (void)hipFree(c->d_image_own);
   if (c->d_present_own) (void)hipFree(c->d_present_own);
   if (c->d_scaled_own) (void)hipFree(c->d_scaled_own);
@@ -561,11 +567,16 @@ int rt_enable_pipelining(rt_ctx* c, int on, void* output_stream) {
     c->out_stream = c->stream;
     return RT_OK;
   }
-  if (c->d_shapes && c->d_shapes != c->d_shapes_buf[0]) {
-    // the current table sits in an rt_compute_frames slot: pipelined frames read header copy k
-    RT_HIP(c, hipMemcpyAsync(c->d_shapes_buf[0], c->d_shapes, c->table.size() * sizeof(float4),
-                             hipMemcpyDeviceToDevice, c->stream));
+  // Pipelined frames read header copy k, the first one copy 0: the table of the header last given
+  // goes there when it sits elsewhere (an rt_compute_frames slot, or another copy; d_shapes itself
+  // may have moved on to a copy that holds an older header, so it is not the source)
+  const float4* cur = c->d_scene ? c->d_scene : c->d_shapes;
+  if (cur && cur != c->d_shapes_buf[0])
+    RT_HIP(c, hipMemcpyAsync(c->d_shapes_buf[0], cur, c->table.size() * sizeof(float4), hipMemcpyDeviceToDevice,
+                             c->stream));
+  if (cur) {
     c->d_shapes = c->d_shapes_buf[0];
+    if (c->d_scene) c->d_scene = c->d_shapes;
     c->d_rb = c->d_rb_buf[0];
   }
   for (int k = 1; k < c->n_ao_streams; ++k)
@@ -634,6 +645,7 @@ int rt_upload_header(rt_ctx* c, const void* header, size_t bytes) {
   rc = staged_copy(c, c->d_shapes_buf[hc], c->table.data(), c->table.size() * sizeof(float4), ao_stream(c));
   if (rc != RT_OK) return rc;
   c->d_shapes = c->d_shapes_buf[hc];
+  c->d_scene = c->d_shapes;
   c->d_rb = c->d_rb_buf[hc];
   c->nobj = nobj;
   c->nplanes = np;
@@ -655,6 +667,7 @@ int rt_upload_rand_buffer(rt_ctx* c, const float* rb, size_t n_vec4) {
     RT_HIP(c, hipMemcpyAsync(c->d_shapes_buf[hc], c->d_shapes, rt::rand_table(table_stride(c)) * sizeof(float4),
                              hipMemcpyDeviceToDevice, ao_stream(c)));
   c->d_shapes = c->d_shapes_buf[hc];
+  c->d_scene = c->d_shapes;
   c->d_rb = c->d_rb_buf[hc];
   return RT_OK;
 }
@@ -805,6 +818,7 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
     if (last != c->table.data()) std::memcpy(c->table.data(), last, tb);
     for (int j = 0; j < m; ++j) {
       c->d_shapes = c->d_batch + (size_t)dslot[j] * tv;
+      c->d_scene = c->d_shapes;
       c->d_rb = c->d_shapes + rt::rand_table(Sc);
       c->nobj = nobj[j];
       c->nplanes = npl[j];
@@ -1124,6 +1138,106 @@ int rt_download_rgba8_scaled(rt_ctx* c, int out_width, int out_height, int top_d
   RT_HIP(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
+
+// ---- ray queries (include/rt/abi.h "Ray queries") -------------------------------------------
+// the scene in effect: the table and camera of the header last given to the context
+static rt::QueryScene query_scene(const rt_ctx* c) {
+  rt::QueryScene s{};
+  s.shapes = c->d_scene;
+  s.S = table_stride(c);
+  s.nobj = c->nobj;
+  s.nplanes = c->nplanes;
+  s.fW = (float)c->cfg.width;
+  s.fH = (float)c->cfg.height;
+  const float *h = hv(c, RT_HDR_HORIZONTAL), *v = hv(c, RT_HDR_VERTICAL), *l = hv(c, RT_HDR_LLC_MINUS_CAMPOS),
+              *cam = hv(c, RT_HDR_CAMERA_LOCATION);
+  s.hx = h[0]; s.hy = h[1]; s.hz = h[2];
+  s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.lx = l[0]; s.ly = l[1]; s.lz = l[2];
+  s.cx = cam[0]; s.cy = cam[1]; s.cz = cam[2];
+  return s;
+}
+static bool query_thr_ok(float thr) { return thr >= 0.0f && thr <= 3.402823466e+38f; }  // finite and >= 0; NaN fails
+// The checks every query starts with, then the main stream ordered behind everything the context
+// has enqueued (the pipelined streams joined with the context's own events: nothing is created).
+// RT_OK: go on; 1: nothing to do (n == 0); else the status to return.
+static int query_begin(rt_ctx* c, size_t n, bool inputs) {
+  if (!c || n > RT_QUERY_MAX_RAYS) return RT_E_INVAL;
+  if (!c->have_header) return RT_E_STATE;
+  if (n == 0) return 1;
+  if (!inputs) return RT_E_INVAL;
+  RT_HIP(c, hipSetDevice(c->device));
+  return join(c);
+}
+#define RT_QUERY_BEGIN(c, n, inputs)         \
+  do {                                       \
+    const int _rc = query_begin(c, n, inputs); \
+    if (_rc != RT_OK) return _rc < 0 ? _rc : RT_OK; \
+  } while (0)
+
+int rt_trace_rays(rt_ctx* c, const float* origins, const float* dirs, size_t n, float thr, float* t, int32_t* ind,
+                  float* normals) {
+  if (!query_thr_ok(thr)) return RT_E_INVAL;
+  RT_QUERY_BEGIN(c, n, origins && dirs);
+  return c->query.trace(query_scene(c), origins, dirs, nullptr, n, thr, t, ind, normals, nullptr, c->stream, c->last_hip);
+}
+
+int rt_trace_pixels(rt_ctx* c, const int32_t* xy, size_t n, float thr, float* t, int32_t* ind, float* normals,
+                    float* dirs) {
+  if (!query_thr_ok(thr)) return RT_E_INVAL;
+  RT_QUERY_BEGIN(c, n, xy != nullptr);
+  return c->query.trace(query_scene(c), nullptr, nullptr, xy, n, thr, t, ind, normals, dirs, c->stream, c->last_hip);
+}
+
+int rt_occluded(rt_ctx* c, const float* from, const float* to, size_t n, uint8_t* out) {
+  RT_QUERY_BEGIN(c, n, from && to);
+  if (!out) return RT_OK;
+  return c->query.occluded(query_scene(c), from, to, n, out, c->stream, c->last_hip);
+}
+
+int rt_trace_rays_device(rt_ctx* c, const void* d_origins, const void* d_dirs, size_t n, float thr, void* d_t,
+                         void* d_ind, void* d_normals) {
+  if (!query_thr_ok(thr)) return RT_E_INVAL;
+  RT_QUERY_BEGIN(c, n, d_origins && d_dirs);
+  rt::RayQuery q{};
+  q.sc = query_scene(c);
+  q.origins = (const float*)d_origins;
+  q.dirs = (const float*)d_dirs;
+  q.n = n;
+  q.thr = thr;
+  q.t = (float*)d_t;
+  q.ind = (int*)d_ind;
+  q.nrm = (float*)d_normals;
+  RT_HIP(c, rt::launch_ray_query(q, c->stream));
+  return RT_OK;
+}
+
+int rt_trace_pixels_device(rt_ctx* c, const void* d_xy, size_t n, float thr, void* d_t, void* d_ind, void* d_normals,
+                           void* d_dirs) {
+  if (!query_thr_ok(thr)) return RT_E_INVAL;
+  RT_QUERY_BEGIN(c, n, d_xy != nullptr);
+  rt::RayQuery q{};
+  q.sc = query_scene(c);
+  q.xy = (const int*)d_xy;
+  q.n = n;
+  q.thr = thr;
+  q.t = (float*)d_t;
+  q.ind = (int*)d_ind;
+  q.nrm = (float*)d_normals;
+  q.dir_out = (float*)d_dirs;
+  RT_HIP(c, rt::launch_ray_query(q, c->stream));
+  return RT_OK;
+}
+
+int rt_occluded_device(rt_ctx* c, const void* d_from, const void* d_to, size_t n, void* d_out) {
+  RT_QUERY_BEGIN(c, n, d_from && d_to);
+  if (!d_out) return RT_OK;
+  RT_HIP(c, rt::launch_occluded(query_scene(c), (const float*)d_from, (const float*)d_to, n, (unsigned char*)d_out,
+                                c->stream));
+  return RT_OK;
+}
+
+size_t rt_query_workspace_bytes(rt_ctx* c) { return c ? c->query.bytes : 0; }
 
 // ---- host-buffer parity path -----------------------------------------------------------
 // the SSBO's pixel, normals and depth arrays (whole-frame contexts)

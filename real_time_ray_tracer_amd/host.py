@@ -177,6 +177,43 @@ class GBuffer:
     image: np.ndarray    # [R][W][4]
 
 
+@dataclass
+class Hits:
+    """Closest hits of n rays: t [n] float32 (-1: a miss), ind [n] int32 (-1: a miss), normals [n][3]
+    float32 (zeros for a miss); dirs [n][3]: the rays used, for pixel rays (else None)."""
+    t: np.ndarray
+    ind: np.ndarray
+    normals: np.ndarray
+    dirs: np.ndarray | None = None
+
+    @classmethod
+    def empty(cls, n: int, dirs: bool = False) -> "Hits":
+        return cls(np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32),
+                   np.zeros((n, 3), np.float32) if dirs else None)
+
+
+def _rows(a, w: int, dtype) -> np.ndarray:
+    """a as a C-contiguous [n][w] array of dtype (integers are neither truncated from floats nor
+    wrapped from beyond int32)."""
+    a = np.asarray(a)
+    if dtype == np.int32 and a.size:
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("pixel coordinates must be integers")
+        if a.min() < -2**31 or a.max() > 2**31 - 1:
+            raise ValueError("pixel coordinates must fit in int32")
+    if a.size % w:
+        raise ValueError(f"need rows of {w} values, got shape {a.shape}")
+    return np.ascontiguousarray(a.reshape(-1, w), dtype)
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _dptr(p):
+    return C.c_void_p(int(p)) if p else None
+
+
 class Renderer:
     """One rt_ctx: a device, a frame (or a row strip of it), a resident g-buffer ring."""
 
@@ -341,6 +378,59 @@ class Renderer:
     def bind_image(self, device_ptr: int | None):
         self._c(self._lib.rt_bind_image(self.ctx, C.c_void_p(device_ptr) if device_ptr else None),
                 "rt_bind_image")
+
+    # ray queries on the scene in effect (include/rt/abi.h "Ray queries")
+    def trace_rays(self, origins, dirs, thr: float = 1e-4) -> "Hits":
+        """Closest hits of the rays (origins[i], dirs[i]) ([n][3] each; dirs used as given, not
+        normalised) accepted for t > thr (rt_trace_rays): Hits(t, ind, normals), -1 / -1 / zeros for a miss."""
+        o, d = _rows(origins, 3, np.float32), _rows(dirs, 3, np.float32)
+        if len(o) != len(d):
+            raise ValueError(f"trace_rays: {len(o)} origins, {len(d)} directions")
+        h = Hits.empty(len(o))
+        self._c(self._lib.rt_trace_rays(self.ctx, fptr(o), fptr(d), len(o), thr, fptr(h.t), _iptr(h.ind),
+                                        fptr(h.normals)), "rt_trace_rays")
+        return h
+
+    def trace_pixels(self, xy, thr: float = 0.0) -> "Hits":
+        """Closest hits of the camera's rays through the pixels xy ([n][2] ints, frame coordinates,
+        row 0 = the bottom row; rt_trace_pixels): Hits(t, ind, normals, dirs), dirs the rays used.
+        thr 0: what a mode-3 frame shows at the pixel; 0.001: mode 4; 0.0001: the AO modes."""
+        p = _rows(xy, 2, np.int32)
+        h = Hits.empty(len(p), dirs=True)
+        self._c(self._lib.rt_trace_pixels(self.ctx, _iptr(p), len(p), thr, fptr(h.t), _iptr(h.ind), fptr(h.normals),
+                                          fptr(h.dirs)), "rt_trace_pixels")
+        return h
+
+    def occluded(self, a, b) -> np.ndarray:
+        """Whether something lies between a[i] and b[i] as a shadow ray from a[i] to a light at b[i]
+        sees it (rt_occluded): bool [n]."""
+        a, b = _rows(a, 3, np.float32), _rows(b, 3, np.float32)
+        if len(a) != len(b):
+            raise ValueError(f"occluded: {len(a)} start points, {len(b)} end points")
+        out = np.zeros(len(a), np.uint8)
+        self._c(self._lib.rt_occluded(self.ctx, fptr(a), fptr(b), len(a), out.ctypes.data_as(C.c_void_p)),
+                "rt_occluded")
+        return out.astype(bool)
+
+    # the same on device memory: integer device pointers (a torch tensor's data_ptr()), 0 / None =
+    # that output is not wanted; enqueued on the context's stream, no wait (rt_*_device)
+    def trace_rays_device(self, d_origins: int, d_dirs: int, n: int, thr: float = 1e-4, d_t=None, d_ind=None,
+                          d_normals=None):
+        self._c(self._lib.rt_trace_rays_device(self.ctx, _dptr(d_origins), _dptr(d_dirs), int(n), thr, _dptr(d_t),
+                                               _dptr(d_ind), _dptr(d_normals)), "rt_trace_rays_device")
+
+    def trace_pixels_device(self, d_xy: int, n: int, thr: float = 0.0, d_t=None, d_ind=None, d_normals=None,
+                            d_dirs=None):
+        self._c(self._lib.rt_trace_pixels_device(self.ctx, _dptr(d_xy), int(n), thr, _dptr(d_t), _dptr(d_ind),
+                                                 _dptr(d_normals), _dptr(d_dirs)), "rt_trace_pixels_device")
+
+    def occluded_device(self, d_from: int, d_to: int, n: int, d_out=None):
+        self._c(self._lib.rt_occluded_device(self.ctx, _dptr(d_from), _dptr(d_to), int(n), _dptr(d_out)),
+                "rt_occluded_device")
+
+    def query_workspace_bytes(self) -> int:
+        """Bytes of the host-pointer queries' device workspace (0 until the first such query)."""
+        return int(self._lib.rt_query_workspace_bytes(self.ctx))
 
     # 8-bit display output (the blit, src/main.cpp:783-797)
     def present(self, top_down: bool = True):
@@ -644,6 +734,45 @@ def resample_rgba8(image, out_w: int, out_h: int, top_down: bool = True) -> np.n
     _check(_lib.load().rt_resample_rgba8(fptr(im), im.shape[1], im.shape[0], int(out_w), int(out_h),
                                          int(bool(top_down)), out.ctypes.data_as(C.c_void_p)), "rt_resample_rgba8")
     return out
+
+
+def _query_cfg(header: Header, width: int = 1, height: int = 1):
+    return _lib.rt_config(int(width), int(height), header.S, header.AA, 1, 1, 0, 0)
+
+
+def trace_rays_host(header: Header, origins, dirs, thr: float = 1e-4) -> Hits:
+    """rt_trace_rays_host (host only): Renderer.trace_rays' rule in C on `header`, its specification."""
+    o, d = _rows(origins, 3, np.float32), _rows(dirs, 3, np.float32)
+    if len(o) != len(d):
+        raise ValueError(f"trace_rays_host: {len(o)} origins, {len(d)} directions")
+    h = Hits.empty(len(o))
+    _check(_lib.load().rt_trace_rays_host(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
+                                          header.data.nbytes, fptr(o), fptr(d), len(o), thr, fptr(h.t), _iptr(h.ind),
+                                          fptr(h.normals)), "rt_trace_rays_host")
+    return h
+
+
+def pixel_rays_host(header: Header, width: int, height: int, xy):
+    """rt_pixel_rays_host (host only): (origins, dirs) [n][3] of the camera's rays through the pixels
+    xy ([n][2] ints) of a width x height frame, the rays Renderer.trace_pixels traces."""
+    p = _rows(xy, 2, np.int32)
+    o, d = np.zeros((len(p), 3), np.float32), np.zeros((len(p), 3), np.float32)
+    _check(_lib.load().rt_pixel_rays_host(C.byref(_query_cfg(header, width, height)),
+                                          header.data.ctypes.data_as(C.c_void_p), header.data.nbytes, _iptr(p), len(p),
+                                          fptr(o), fptr(d)), "rt_pixel_rays_host")
+    return o, d
+
+
+def occluded_host(header: Header, a, b) -> np.ndarray:
+    """rt_occluded_host (host only): Renderer.occluded's rule in C on `header`, its specification."""
+    a, b = _rows(a, 3, np.float32), _rows(b, 3, np.float32)
+    if len(a) != len(b):
+        raise ValueError(f"occluded_host: {len(a)} start points, {len(b)} end points")
+    out = np.zeros(len(a), np.uint8)
+    _check(_lib.load().rt_occluded_host(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
+                                        header.data.nbytes, fptr(a), fptr(b), len(a), out.ctypes.data_as(C.c_void_p)),
+           "rt_occluded_host")
+    return out.astype(bool)
 
 
 def plan_strips(row_cost, n: int) -> list[int]:
