@@ -512,16 +512,26 @@ int rt_host_stats(rt_ctx* ctx, double* wait_ms, long long* waits);
  * segments (one scene loop each), [2] shadow rays, [3] ray-shape tests = ([1] + [2]) *
  * int(mode.z) — the algorithmic-FLOP basis of the roofline (20 FLOP per ray-sphere test,
  * SURVEY.md §8d), [4] executed lane-tests = sum over wavefronts of 64 x the shapes their scene
- * loops tested (divergence and culling: [3]/[4] is the useful fraction); post-process:
+ * loops tested (divergence and culling: [3]/[4] is the useful fraction; modes 3/4 count 64 x the
+ * longest lane's (segments + shadow rays) x int(mode.z) per wavefront of 8 x 8 pixels; an AO pool
+ * whose cull keeps no sphere runs no sphere test beyond the cull, which is then the scene loop of
+ * its primary segments: 64 x the cull's rounds of the wave, ceil(int(mode.z) / 64)); post-process:
  * [5] filtered pixels (those with a primary hit, normals.w > 0.99; the others are copied),
  * [6] history slots read, [7] history slots accepted. */
 int rt_enable_counters(rt_ctx* ctx, int on);
 /* Read the 8 totals (synchronises); reset != 0 zeroes them afterwards. */
 int rt_read_counters(rt_ctx* ctx, uint64_t out[8], int reset);
-/* Per-row work of this context's rows (R = row_end - row_begin entries), collected while
- * row counters are on: segments + shadow rays (modes 3/4, simple AO kernel), or an estimate in
- * sphere-test units (pooled AO kernel: per-sample setup + culled primary tests + bounce tests).
- * The cost profile used to balance row strips across GPUs. */
+/* Per-row work of this context's rows (R = row_end - row_begin entries; a strip's halo rows are
+ * traced and counted in the totals above, but not returned here), collected while row counters
+ * are on.  Modes 3/4: segments + shadow rays of the row's pixels, exactly.  Modes 1/2 (the pooled
+ * AO kernel): an estimate in sphere-test units, per sample of s segments
+ *   kSetupCost + ncull + (s >= 2 ? b1cost + (s - 2) * nobj : 0)
+ * with kSetupCost = 24 the per-sample setup, ncull <= nobj the spheres the pool's primary-ray cull
+ * kept and b1cost <= nobj those the latest batched first bounce tested; a pool whose cull keeps no
+ * sphere takes the empty-frustum shortcut and adds spp per pixel (1 per sample) instead.  ncull and
+ * b1cost depend on the culls and on how samples are batched, not on the reference algorithm, so
+ * the tests bound these rows (tests/trace_counts.py ao_row_bounds) where they check modes 3/4
+ * exactly.  The cost profile used to balance row strips across GPUs. */
 int rt_read_row_counters(rt_ctx* ctx, uint64_t* rows, int reset);
 
 /* ---- device math self-test (parity of the shared float semantics) ------------------ */

@@ -70,6 +70,12 @@ def load():
     lib.rto_run_program_window.restype = C.c_int
     lib.rto_dispatch.argtypes = [fp, C.POINTER(rto_dims), C.c_int, C.c_int, fp, C.c_int]
     lib.rto_dispatch.restype = C.c_int
+    if hasattr(lib, "rto_dispatch_counted"):  # (absent from older builds, as rto_sin_check_range below)
+        up = C.POINTER(C.c_uint32)
+        lib.rto_run_program_window_counted.argtypes = lib.rto_run_program_window.argtypes + [up, up, up]
+        lib.rto_run_program_window_counted.restype = C.c_int
+        lib.rto_dispatch_counted.argtypes = lib.rto_dispatch.argtypes + [up, up, up]
+        lib.rto_dispatch_counted.restype = C.c_int
     lib.rto_sin.argtypes = [C.c_float]
     lib.rto_sin.restype = C.c_float
     if hasattr(lib, "rto_sin_check_range"):  # (absent from older builds, tools/sin_change_effect.py)
@@ -107,23 +113,42 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _up(a, d):
+    if a is None:
+        return None
+    assert a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"] and a.shape == (d.gh, d.W)
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 def dims(W, H, S, AA, F=8, D=20, gy0=0, gh=None) -> rto_dims:
     return rto_dims(W, H, S, AA, F, D, gy0, H if gh is None else gh)
 
 
 def run_program(ssbo: np.ndarray, d: rto_dims, program: int, frame: int, image=None, y0=None, y1=None,
-                nthreads: int = 0, x0: int = 0, x1=None) -> None:
-    """Rows [y0, y1) (default: the g-buffer band) x columns [x0, x1) (default: all)."""
+                nthreads: int = 0, x0: int = 0, x1=None, segs=None, shadows=None, single=None) -> None:
+    """Rows [y0, y1) (default: the g-buffer band) x columns [x0, x1) (default: all).  segs, shadows,
+    single: optional uint32 [gh][W] planes (row 0 = gy0) that receive the window's per-pixel work
+    (closest-hit scene loops, shadow rays, samples of exactly one loop: rto_run_program_window_counted)."""
     y0 = d.gy0 if y0 is None else y0
     y1 = d.gy0 + d.gh if y1 is None else y1
     x1 = d.W if x1 is None else x1
-    rc = load().rto_run_program_window(_fp(ssbo), C.byref(d), program, frame, _fp(image), y0, y1, x0, x1, nthreads)
+    if segs is None and shadows is None and single is None:
+        rc = load().rto_run_program_window(_fp(ssbo), C.byref(d), program, frame, _fp(image), y0, y1, x0, x1, nthreads)
+    else:
+        rc = load().rto_run_program_window_counted(_fp(ssbo), C.byref(d), program, frame, _fp(image), y0, y1, x0, x1,
+                                                   nthreads, _up(segs, d), _up(shadows, d), _up(single, d))
     if rc != 0:
         raise ValueError(f"rto_run_program rejected its arguments (program {program})")
 
 
-def dispatch(ssbo: np.ndarray, d: rto_dims, mode: int, frame: int, image=None, nthreads: int = 0) -> int:
-    rc = load().rto_dispatch(_fp(ssbo), C.byref(d), mode, frame, _fp(image), nthreads)
+def dispatch(ssbo: np.ndarray, d: rto_dims, mode: int, frame: int, image=None, nthreads: int = 0, segs=None,
+             shadows=None, single=None) -> int:
+    """segs, shadows, single: as in run_program (the trace pass of the mode; rto_dispatch_counted)."""
+    if segs is None and shadows is None and single is None:
+        rc = load().rto_dispatch(_fp(ssbo), C.byref(d), mode, frame, _fp(image), nthreads)
+    else:
+        rc = load().rto_dispatch_counted(_fp(ssbo), C.byref(d), mode, frame, _fp(image), nthreads, _up(segs, d),
+                                         _up(shadows, d), _up(single, d))
     if rc < 0:
         raise ValueError(f"rto_dispatch rejected its arguments (mode {mode})")
     return rc

@@ -172,12 +172,21 @@ class Frame:
         if image is not None:
             image[y - gy0, x] = col
 
-    def p_compute(self, x, y, image, gy0):
+    @staticmethod
+    def _work(stats, x, y, segs, shadows, single):
+        """stats (an optional dict) gets the per-pixel work, in the order of x, y: segs = closest-hit
+        scene loops (closest() calls the pixel took part in, summed over its samples), shadows =
+        shadow rays cast (shadow_lit() calls), single = its samples that ran exactly one loop."""
+        if stats is not None:
+            stats.update(x=x, y=y, segs=segs, shadows=shadows, single=single)
+
+    def p_compute(self, x, y, image, gy0, stats=None):
         dirs = self.primary(x, y)
         cam = np.broadcast_to(self.hdr[4, :3], dirs.shape)
         t, ind = self.closest(cam, dirs, 0.0)
         res = np.broadcast_to(self.hdr[6], (len(x), 4)).astype(F).copy()
         hit = ind >= 0
+        self._work(stats, x, y, np.ones(len(x), np.int64), hit.astype(np.int64), np.ones(len(x), np.int64))
         if hit.any():
             curr = cam[hit] + t[hit, None] * dirs[hit]
             lit = self.shadow_lit(curr)
@@ -189,8 +198,9 @@ class Frame:
         col = np.concatenate([np.power(F(0.0) + res[:, :3], GAMMA), np.zeros((len(x), 1), F)], 1).astype(F)
         self.store(x, y, col, image, gy0)
 
-    def h_compute(self, x, y, image, gy0):
+    def h_compute(self, x, y, image, gy0, stats=None):
         n = len(x)
+        segs, shadows = np.zeros(n, np.int64), np.zeros(n, np.int64)
         dirs = self.primary(x, y)
         pos = np.broadcast_to(self.hdr[4, :3], dirs.shape).astype(F).copy()
         res = np.zeros((n, 4), F)
@@ -202,11 +212,13 @@ class Frame:
             if idx.size == 0:
                 break
             t, ind = self.closest(pos[idx], dirs[idx], 0.001)
+            segs[idx] += 1
             att = np.broadcast_to(self.hdr[6], (idx.size, 4)).astype(F).copy()
             stop = np.ones(idx.size, bool)
             hit = ind >= 0
             if hit.any():
                 hi = idx[hit]
+                shadows[hi] += 1
                 curr = pos[hi] + t[hit, None] * dirs[hi]
                 lit = self.shadow_lit(curr)
                 out, nn = self.phong_terms(ind[hit], curr, dirs[hi], self.shapes[ind[hit], 4], lit)
@@ -229,9 +241,11 @@ class Frame:
             live[idx[stop]] = False
         col = np.concatenate([np.power(F(0.0) + res[:, :3], GAMMA), np.zeros((n, 1), F)], 1).astype(F)
         self.store(x, y, col, image, gy0)
+        self._work(stats, x, y, segs, shadows, (segs == 1).astype(np.int64))
 
-    def ao_compute(self, x, y, image, gy0, write_image):
+    def ao_compute(self, x, y, image, gy0, write_image, stats=None):
         n, D, f = len(x), self.D, self.frame
+        segs, single = np.zeros(n, np.int64), np.zeros(n, np.int64)
         gy = y - gy0
         px, py = x.astype(F), y.astype(F)
         cam = self.hdr[4, :3]
@@ -265,11 +279,13 @@ class Frame:
             res = np.ones((n, 4), F)
             pos = np.broadcast_to(cam, (n, 3)).astype(F).copy()
             live = np.ones(n, bool)
+            before = segs.copy()
             for depth in range(D, 0, -1):
                 idx = np.nonzero(live)[0]
                 if idx.size == 0:
                     break
                 t, ind = self.closest(pos[idx], dirs[idx], 0.0001)
+                segs[idx] += 1
                 miss = ind < 0
                 att = np.empty((idx.size, 4), F)
                 att[miss] = self.hdr[6]
@@ -308,11 +324,13 @@ class Frame:
                 res[idx] = res[idx] * att
                 live[stopped] = False
             acc = (acc + res).astype(F)
+            single += segs - before == 1
         fa = F(self.AA)
         acc = (acc / fa).astype(F)
         self.dep[f, x, gy] = (self.dep[f, x, gy] / fa).astype(F)
         col = np.concatenate([np.power(acc[:, :3], GAMMA), np.zeros((n, 1), F)], 1).astype(F)
         self.store(x, y, col, image if write_image else None, gy0)
+        self._work(stats, x, y, segs, np.zeros(n, np.int64), single)
 
     def aop_postprocessing(self, x, y, image, gy0, gh, stats=None):
         """stats: an optional dict, filled per pixel (in the order of x, y) with what the filter did:
@@ -386,11 +404,11 @@ def run_program(ssbo, W, H, S, AA, program, frame, image=None, F_=8, D=20, gy0=0
     ys, xs = np.meshgrid(np.arange(y0, y1), np.arange(W), indexing="ij")
     x, y = xs.ravel(), ys.ravel()
     if program == P_COMPUTE:
-        fr.p_compute(x, y, image, gy0)
+        fr.p_compute(x, y, image, gy0, stats)
     elif program == H_COMPUTE:
-        fr.h_compute(x, y, image, gy0)
+        fr.h_compute(x, y, image, gy0, stats)
     elif program in (AO_COMPUTE, AOP_COMPUTE):
-        fr.ao_compute(x, y, image, gy0, program == AO_COMPUTE)
+        fr.ao_compute(x, y, image, gy0, program == AO_COMPUTE, stats)
     elif program == AOP_POSTPROCESSING:
         fr.aop_postprocessing(x, y, image, gy0, gh, stats)
     else:

@@ -136,7 +136,26 @@ typedef struct {
   int nsoa;
   int* planes;
   int nplanes;
+  /* optional per-pixel work planes [gh][W], row 0 = gy0 (rto_run_program_window_counted): each
+     entry is written by the thread that renders its pixel */
+  uint32_t* cseg;
+  uint32_t* cshad;
+  uint32_t* csingle;
 } octx;
+
+/* a pixel's work: closest-hit scene loops run and shadow rays cast, summed over its samples, and
+   how many of its samples' paths ran exactly one scene loop */
+typedef struct { uint32_t segs, shadows, single; } pwork;
+
+/* one sample's path is over: it ran the scene loops counted since `before` */
+static inline void path_done(pwork* w, uint32_t before) { w->single += (w->segs - before == 1); }
+
+static inline void store_work(const octx* c, int x, int y, pwork w) {
+  const size_t o = (size_t)(y - c->d->gy0) * c->d->W + x;
+  if (c->cseg) c->cseg[o] = w.segs;
+  if (c->cshad) c->cshad[o] = w.shadows;
+  if (c->csingle) c->csingle[o] = w.single;
+}
 
 #define SH(c, i, j, k) ((c)->shapes[((size_t)(i) * 5 + (j)) * 4 + (k)])
 
@@ -174,6 +193,7 @@ static int octx_init(octx* c, float* ssbo, const rto_dims* d, int frame) {
   c->soa = NULL;
   c->planes = NULL;
   c->nsoa = c->nplanes = 0;
+  c->cseg = c->cshad = c->csingle = NULL;
   return 0;
 }
 
@@ -523,13 +543,15 @@ static v4 gamma4(v4 r) {
 /* ------------------------------------------------------------------------------------ */
 /* mode 3: p_compute.glsl:168-245                                                        */
 /* ------------------------------------------------------------------------------------ */
-static v4 phong(const octx* c, v3 dir) {
+static v4 phong(const octx* c, v3 dir, pwork* w) {
   v4 out;
   float t;
   int ind = closest_hit(c, c->cam, dir, 0.0f, &t);
+  w->segs += 1;
   if (ind == -1) return c->bg;
   v3 curr = add3(c->cam, scl3(t, dir));
   int lit = shadow_ray(c, curr);
+  w->shadows += 1;
   v3 n = shape_normal(c, ind, curr);
   v3 col = mk3(SH(c, ind, 4, 0), SH(c, ind, 4, 1), SH(c, ind, 4, 2));
   if (lit) {
@@ -552,9 +574,12 @@ static v4 phong(const octx* c, v3 dir) {
 static void p_main(octx* c, int x, int y, float* image) {
   float hp = (float)x / (float)c->d->W;
   float vp = (float)y / (float)c->d->H;
-  v4 r = phong(c, primary_dir(c, hp, vp));
+  pwork w = {0, 0, 0};
+  v4 r = phong(c, primary_dir(c, hp, vp), &w);
+  path_done(&w, 0);
   v4 acc = {0.0f + r.x, 0.0f + r.y, 0.0f + r.z, 0.0f + r.w};
   store_out(c, x, y, gamma4(acc), image, 1);
+  store_work(c, x, y, w);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -562,10 +587,11 @@ static void p_main(octx* c, int x, int y, float* image) {
 /* ------------------------------------------------------------------------------------ */
 typedef struct { v4 a0; v3 pos; float stop; v3 dir; float refl; } hstate;
 
-static void hybrid_helper(const octx* c, hstate* s, int depth) {
+static void hybrid_helper(const octx* c, hstate* s, int depth, pwork* w) {
   if (depth <= 0) { v4 z = {0, 0, 0, 0}; s->a0 = z; } /* h_compute.glsl:188-189 (unreachable) */
   float t;
   int ind = closest_hit(c, s->pos, s->dir, 0.001f, &t);
+  w->segs += 1;
   if (ind == -1) {
     s->a0 = c->bg;
     s->stop = 1.0f;
@@ -574,6 +600,7 @@ static void hybrid_helper(const octx* c, hstate* s, int depth) {
   v4 att = {SH(c, ind, 4, 0), SH(c, ind, 4, 1), SH(c, ind, 4, 2), SH(c, ind, 4, 3)};
   v3 curr = add3(s->pos, scl3(t, s->dir));
   int lit = shadow_ray(c, curr);
+  w->shadows += 1;
   v3 n = shape_normal(c, ind, curr);
   if (lit) {
     v3 l = nrm3(sub3(c->light, curr));
@@ -603,19 +630,19 @@ static void hybrid_helper(const octx* c, hstate* s, int depth) {
   s->a0 = att;
 }
 
-static v4 hybrid(const octx* c, v3 dir) {
+static v4 hybrid(const octx* c, v3 dir, pwork* w) {
   hstate s;
   s.pos = c->cam;
   s.stop = 0.0f;
   s.dir = dir;
   s.refl = 0.0f;
-  hybrid_helper(c, &s, c->d->D);
+  hybrid_helper(c, &s, c->d->D, w);
   float cc = s.refl;
   v4 res = s.a0;
   if (s.stop == 1.0f) return res;
   int i = c->d->D - 1;
   while (i > 0) {
-    hybrid_helper(c, &s, i);
+    hybrid_helper(c, &s, i, w);
     float den = 1.0f + cc;
     res.x = (res.x + cc * s.a0.x) / den;
     res.y = (res.y + cc * s.a0.y) / den;
@@ -631,9 +658,12 @@ static v4 hybrid(const octx* c, v3 dir) {
 static void h_main(octx* c, int x, int y, float* image) {
   float hp = (float)x / (float)c->d->W;
   float vp = (float)y / (float)c->d->H;
-  v4 r = hybrid(c, primary_dir(c, hp, vp));
+  pwork w = {0, 0, 0};
+  v4 r = hybrid(c, primary_dir(c, hp, vp), &w);
+  path_done(&w, 0);
   v4 acc = {0.0f + r.x, 0.0f + r.y, 0.0f + r.z, 0.0f + r.w};
   store_out(c, x, y, gamma4(acc), image, 1);
+  store_work(c, x, y, w);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -658,7 +688,7 @@ static v3 get_pt_within_unit_sphere(const octx* c, int aa, int x, int y) {
 
 typedef struct { v4 a0; v3 pos; float stop; v3 dir; } aostate;
 
-static void ao_helper(octx* c, aostate* s, int depth, int aa, int x, int y, v3 hemi) {
+static void ao_helper(octx* c, aostate* s, int depth, int aa, int x, int y, v3 hemi, pwork* w) {
   size_t g = gidx(c, c->frame, x, y);
   if (depth <= 0) { /* ao_compute.glsl:163-172 (unreachable: depth >= 1) */
     v4 z = {0, 0, 0, 0};
@@ -669,6 +699,7 @@ static void ao_helper(octx* c, aostate* s, int depth, int aa, int x, int y, v3 h
   }
   float t;
   int ind = closest_hit(c, s->pos, s->dir, 0.0001f, &t);
+  w->segs += 1;
   if (ind != -1) {
     v4 att = {SH(c, ind, 4, 0), SH(c, ind, 4, 1), SH(c, ind, 4, 2), SH(c, ind, 4, 3)};
     if (SH(c, ind, 1, 3) > 0.9f) { /* emissive */
@@ -714,7 +745,7 @@ static void ao_helper(octx* c, aostate* s, int depth, int aa, int x, int y, v3 h
   c->dep[g + 1] = (float)(c->d->D - depth);
 }
 
-static v4 ambient_occlusion(octx* c, v3 dir, int aa, int x, int y) {
+static v4 ambient_occlusion(octx* c, v3 dir, int aa, int x, int y, pwork* w) {
   v4 res = {1.0f, 1.0f, 1.0f, 1.0f};
   aostate s;
   s.pos = c->cam;
@@ -722,9 +753,10 @@ static v4 ambient_occlusion(octx* c, v3 dir, int aa, int x, int y) {
   s.dir = dir;
   /* get_pt_within_unit_sphere depends only on (aa, x, y): same value every bounce */
   v3 hemi = get_pt_within_unit_sphere(c, aa, x, y);
+  const uint32_t before = w->segs;
   int i = c->d->D;
   while (i > 0) {
-    ao_helper(c, &s, i, aa, x, y, hemi);
+    ao_helper(c, &s, i, aa, x, y, hemi, w);
     res.x = res.x * s.a0.x;
     res.y = res.y * s.a0.y;
     res.z = res.z * s.a0.z;
@@ -732,6 +764,7 @@ static v4 ambient_occlusion(octx* c, v3 dir, int aa, int x, int y) {
     if ((int)s.stop == 1) break;
     i -= 1;
   }
+  path_done(w, before);
   return res;
 }
 
@@ -739,11 +772,12 @@ static void ao_main(octx* c, int x, int y, float* image, int write_image) {
   const int AA = c->d->AA;
   const float* rb = c->rb;
   v4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  pwork wk = {0, 0, 0};
   float px = (float)x, py = (float)y;
   {
     float hp = px / (float)c->d->W;
     float vp = py / (float)c->d->H;
-    v4 r = ambient_occlusion(c, primary_dir(c, hp, vp), 0, x, y);
+    v4 r = ambient_occlusion(c, primary_dir(c, hp, vp), 0, x, y, &wk);
     acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
   }
   for (int aa = 1; aa < AA; aa++) {
@@ -766,7 +800,7 @@ static void ao_main(octx* c, int x, int y, float* image, int write_image) {
     float jy = (w * il) / 6.0f - 0.08333f;
     float hp = (px + jx) / (float)c->d->W;
     float vp = (py + jy) / (float)c->d->H;
-    v4 r = ambient_occlusion(c, primary_dir(c, hp, vp), aa, x, y);
+    v4 r = ambient_occlusion(c, primary_dir(c, hp, vp), aa, x, y, &wk);
     acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
   }
   float fa = (float)AA;
@@ -774,6 +808,7 @@ static void ao_main(octx* c, int x, int y, float* image, int write_image) {
   size_t g = gidx(c, c->frame, x, y);
   for (int k = 0; k < 4; k++) c->dep[g + k] /= fa; /* depth_buffer[frame][x][y] /= AA */
   store_out(c, x, y, gamma4(acc), image, write_image);
+  store_work(c, x, y, wk);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -850,10 +885,14 @@ static void post_main(octx* c, const float* snap /* [W][gh] vec4 */, int x, int 
 /* ------------------------------------------------------------------------------------ */
 /* drivers                                                                               */
 /* ------------------------------------------------------------------------------------ */
-int rto_run_program_window(float* ssbo, const rto_dims* d, int program, int frame, float* image, int y0,
-                           int y1, int x0, int x1, int nthreads) {
+int rto_run_program_window_counted(float* ssbo, const rto_dims* d, int program, int frame, float* image, int y0,
+                                   int y1, int x0, int x1, int nthreads, uint32_t* segs, uint32_t* shadows,
+                                   uint32_t* single) {
   octx c;
   if (octx_init(&c, ssbo, d, frame) != 0) return -1;
+  c.cseg = segs;
+  c.cshad = shadows;
+  c.csingle = single;
   if (y0 < d->gy0 || y1 > d->gy0 + d->gh || y0 > y1) return -1;
   if (x0 < 0 || x1 > d->W || x0 > x1) return -1;
   if (program < RTO_AOP_COMPUTE || program > RTO_H_COMPUTE) return -1;
@@ -900,23 +939,36 @@ int rto_run_program_window(float* ssbo, const rto_dims* d, int program, int fram
   return 0;
 }
 
+int rto_run_program_window(float* ssbo, const rto_dims* d, int program, int frame, float* image, int y0,
+                           int y1, int x0, int x1, int nthreads) {
+  return rto_run_program_window_counted(ssbo, d, program, frame, image, y0, y1, x0, x1, nthreads, NULL, NULL, NULL);
+}
+
 int rto_run_program(float* ssbo, const rto_dims* d, int program, int frame, float* image, int y0,
                     int y1, int nthreads) {
   return d ? rto_run_program_window(ssbo, d, program, frame, image, y0, y1, 0, d->W, nthreads) : -1;
 }
 
-int rto_dispatch(float* ssbo, const rto_dims* d, int mode, int frame, float* image, int nthreads) {
+int rto_dispatch_counted(float* ssbo, const rto_dims* d, int mode, int frame, float* image, int nthreads,
+                         uint32_t* segs, uint32_t* shadows, uint32_t* single) {
+  if (!d) return -1;
   int y0 = d->gy0, y1 = d->gy0 + d->gh, rc;
+#define RTO_TRACE(prog) rto_run_program_window_counted(ssbo, d, prog, frame, image, y0, y1, 0, d->W, nthreads, segs, shadows, single)
   switch (mode) {
     case 1:
-      rc = rto_run_program(ssbo, d, RTO_AOP_COMPUTE, frame, image, y0, y1, nthreads);
+      rc = RTO_TRACE(RTO_AOP_COMPUTE);
       if (rc == 0) rc = rto_run_program(ssbo, d, RTO_AOP_POSTPROCESSING, frame, image, y0, y1, nthreads);
       break;
-    case 2: rc = rto_run_program(ssbo, d, RTO_AO_COMPUTE, frame, image, y0, y1, nthreads); break;
-    case 3: rc = rto_run_program(ssbo, d, RTO_P_COMPUTE, frame, image, y0, y1, nthreads); break;
-    case 4: rc = rto_run_program(ssbo, d, RTO_H_COMPUTE, frame, image, y0, y1, nthreads); break;
+    case 2: rc = RTO_TRACE(RTO_AO_COMPUTE); break;
+    case 3: rc = RTO_TRACE(RTO_P_COMPUTE); break;
+    case 4: rc = RTO_TRACE(RTO_H_COMPUTE); break;
     default: return -1;
   }
+#undef RTO_TRACE
   if (rc != 0) return rc;
   return (frame + 1) % d->F;
+}
+
+int rto_dispatch(float* ssbo, const rto_dims* d, int mode, int frame, float* image, int nthreads) {
+  return rto_dispatch_counted(ssbo, d, mode, frame, image, nthreads, NULL, NULL, NULL);
 }

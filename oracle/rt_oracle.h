@@ -69,6 +69,22 @@ int rto_run_program_window(float* ssbo, const rto_dims* d, int program, int fram
  * next frame slot. */
 int rto_dispatch(float* ssbo, const rto_dims* d, int mode, int frame, float* image, int nthreads);
 
+/* The same two calls with the work of every traced pixel as an optional output: segs, shadows
+ * and single are [gh][W] uint32 planes (row 0 = gy0; any may be NULL).  segs[y][x] = the
+ * closest-hit scene loops run for pixel (x, y), summed over its samples; shadows[y][x] = the
+ * shadow rays cast for it (p_compute: 1 loop, and 1 shadow ray iff the primary ray hits;
+ * h_compute: one loop per hybrid_helper call, one shadow ray per hit; ao_compute /
+ * aop_compute: one loop per ambient_occlusion_helper call of every sample, no shadow rays);
+ * single[y][x] = how many of the pixel's samples ran exactly one scene loop (what splits segs
+ * into per-sample terms: the others ran two or more).
+ * Only the window's pixels are written, each by the thread that renders it; the post-process
+ * program writes none.  Everything else is as without the planes. */
+int rto_run_program_window_counted(float* ssbo, const rto_dims* d, int program, int frame, float* image,
+                                   int y0, int y1, int x0, int x1, int nthreads, uint32_t* segs,
+                                   uint32_t* shadows, uint32_t* single);
+int rto_dispatch_counted(float* ssbo, const rto_dims* d, int mode, int frame, float* image, int nthreads,
+                         uint32_t* segs, uint32_t* shadows, uint32_t* single);
+
 /* primitives (exported for the math self-tests) */
 float rto_sin(float x);
 /* counts the bit patterns start .. start+n-1 (mod 2^32) where got[i] != rto_sin (NaN == NaN),

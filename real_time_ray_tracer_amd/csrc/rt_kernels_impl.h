@@ -1392,6 +1392,9 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
       atomicAdd(&c[0 * kCounterSlots], (unsigned long long)total);
       atomicAdd(&c[1 * kCounterSlots], (unsigned long long)total);
       atomicAdd(&c[3 * kCounterSlots], (unsigned long long)total * (unsigned long long)nobj);
+      // the pool's cull is the scene loop of these segments: every sphere tested once for the whole
+      // pool, one per lane, on nwords rounds of the wave (counted so when the masks were loaded too)
+      atomicAdd(&c[4 * kCounterSlots], 64ull * (unsigned long long)nwords);
     }
     return;
   }
