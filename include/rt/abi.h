@@ -244,7 +244,7 @@ int rt_bind_image(rt_ctx* ctx, void* device_ptr);
  *   h_compute.glsl:199-210, ao_compute.glsl:183-194) with the threshold as a parameter:
  *     t = -1, ind = -1;  for i = 0 .. nobj-1 ascending:  res = eval_ray(o, d, i)
  *       (sphere_eval_ray for a sphere, plane_eval_ray for a plane, -1 for anything else: a
- *       rectangle is never hit);  if (res > thr && (res < t || t < 0)) { t = res; ind = i; }
+ *       rectangle is never hit unless rt_set_rectangles is on, "Rectangles" below);  if (res > thr && (res < t || t < 0)) { t = res; ind = i; }
  *   so the lowest index wins a tie.  d is used as given, NOT normalised (the sphere test assumes a
  *   unit vector, as the reference's does).  Per ray: t (float, -1 for a miss), ind (int32, -1 for a
  *   miss), normal (3 floats): zeros for a miss, the stored normal for a plane, for a sphere
@@ -297,6 +297,44 @@ int rt_pixel_rays_host(const rt_config* cfg, const void* header, size_t header_b
                        float* origins, float* dirs);
 int rt_occluded_host(const rt_config* cfg, const void* header, size_t header_bytes, const float* from, const float* to,
                      size_t n, uint8_t* out);
+
+/* ---- Rectangles ----------------------------------------------------------------------- */
+/* The reference packs rectangles (shape id RT_SHAPE_RECTANGLE) but never intersects them: eval_ray's
+ * rectangle call is commented out (resources/p_compute.glsl:132-135).  That stays the default here.
+ * rt_set_rectangles(ctx, 1) makes every closest-hit loop and every shadow loop of programs 1, 3, 4
+ * and 5 (modes 1-4) and of the three ray queries treat shape id 3 by the rule below; 0 restores the
+ * reference's behaviour; rt_rectangles reads the switch (1 / 0).  The switch takes effect at the
+ * next launch or query: the header last given to the context is packed again, and the cull cache and
+ * the tile schedule start over.  A scene with no rectangle among its first int(mode.z) shapes
+ * launches exactly what it launches with the switch off.
+ *   The rule, for row i as loadShapeBuffer packs it (src/main.cpp:444-467): n = shapes[i][0].xyz,
+ *   up = shapes[i][1].xyz, right = shapes[i][2].xyz, llc = shapes[i][3].xyz; the ray is (pos, dir),
+ *   the ray's own origin and direction in every program (the AO bounces included):
+ *     den = dot(n, dir);  if (den < 0.001f && den > -0.001f) return -1;    plane_eval_ray's test
+ *     t   = dot(n, llc - pos) / den;                                       plane_eval_ray with p0 = llc
+ *     p   = pos + t*dir;  q = p - llc;     per component one multiply, one add, one subtract, binary32,
+ *                                          no contraction
+ *     a   = dot(q, right);  b = dot(q, up);
+ *     return (a >= 0 && a <= dot(right, right) && b >= 0 && b <= dot(up, up)) ? t : -1;
+ *   dot() is the fused chain fma(z, z', fma(y, y', x*x')), `/` the IEEE division.  The edges are
+ *   inclusive, both faces are hit, and a NaN anywhere fails a comparison, so the rectangle is missed.
+ *   With right perpendicular to up this is the rectangle llc + u*right + v*up, u, v in [0, 1];
+ *   otherwise it is the part of the plane that the two slabs 0 <= dot(q, right) <= |right|^2 and
+ *   0 <= dot(q, up) <= |up|^2 enclose, a parallelogram whose sides are perpendicular to right and
+ *   to up, not the one spanned by them.  The normal is the stored n, as for a plane, in shading,
+ *   the g-buffers and the queries.  The tie rule (the lowest index wins) and the thresholds (0,
+ *   0.001, 0.0001; shadow t > 0.0001f in binary64) are unchanged. */
+#define RT_SCENE_RECTANGLES 1
+int rt_set_rectangles(rt_ctx* ctx, int on);
+int rt_rectangles(rt_ctx* ctx); /* 1 = on, 0 = off */
+/* Host only: the rule for one packed shape row (20 floats) and one ray; the row's id is not read. */
+float rt_rectangle_eval_host(const float shape[20], const float pos[3], const float dir[3]);
+/* rt_trace_rays_host / rt_occluded_host with flags: RT_SCENE_RECTANGLES applies the rule to shape
+ * id 3; flags = 0 is rt_trace_rays_host / rt_occluded_host.  Any other bit: RT_E_INVAL. */
+int rt_trace_rays_host_ex(const rt_config* cfg, const void* header, size_t header_bytes, const float* origins,
+                          const float* dirs, size_t n, float thr, int flags, float* t, int32_t* ind, float* normals);
+int rt_occluded_host_ex(const rt_config* cfg, const void* header, size_t header_bytes, const float* from,
+                        const float* to, size_t n, int flags, uint8_t* out);
 
 /* ---- 8-bit display output (the blit, src/main.cpp:783-797) -------------------------- */
 /* The reference ends a frame by drawing the rgba32f image into an 8-bit framebuffer
@@ -421,6 +459,8 @@ int rt_group_enable_pipelining(rt_group* g, int on);
 /* rt_set_phong_gbuffer on every strip; kept, as pipelining is, when rt_group_set_bounds,
  * rt_group_set_plan or rt_group_balance re-create the contexts. */
 int rt_group_set_phong_gbuffer(rt_group* g, int on);
+/* rt_set_rectangles on every strip; kept in the same way. */
+int rt_group_set_rectangles(rt_group* g, int on);
 /* Assemble frames into a caller-owned device buffer of H*W float4 on devices[0] (NULL: the
  * group's own).  Waits for the frames in flight first. */
 int rt_group_bind_frame(rt_group* g, void* device_ptr);
@@ -615,7 +655,10 @@ int rt_moving_light(float* header, int light_movement);
  * default camera (src/main.cpp:98-100), light (-12,8,7), SKY background, mode.z = n_objects.
  * S = capacity >= n_objects. */
 int rt_scenegen(float* header, int S, int n_objects, int AA, uint64_t seed, float aspect);
-/* The reference's built-in scenes 1, 5, 6 (src/scene.h:15-167) with the default camera. */
+/* The reference's built-in scenes 1, 5, 6 (src/scene.h:15-167) with the default camera.  7: scene
+ * 5 with its light as the rectangle the reference left commented out (src/scene.h:80-86): llc
+ * (4, 6, 4), right (0, 0, -8), up (-8, 0, 0), colour 1.5, emissive, in place of the emissive sphere
+ * (drawn only with rt_set_rectangles on). */
 int rt_init_scene(float* header, int S, int AA, int which, float aspect);
 
 const char* rt_strerror(int status);

@@ -27,6 +27,7 @@ RT_MODE_AO_PP, RT_MODE_AO, RT_MODE_PHONG, RT_MODE_PHONG_REFL = 1, 2, 3, 4
 RT_NUM_FRAMES = 8
 RT_RECURSION_DEPTH = 20
 RT_SHAPE_SPHERE, RT_SHAPE_RECTANGLE, RT_SHAPE_PLANE = 1, 3, 5
+RT_SCENE_RECTANGLES = 1  # flags of the _ex host functions: shape id 3 follows the rectangle rule
 HDR_MODE, HDR_HORIZONTAL, HDR_VERTICAL, HDR_LLC, HDR_CAMERA, HDR_LIGHT, HDR_BACKGROUND = range(7)
 
 
@@ -63,6 +64,8 @@ SIGNATURES = {
     "rt_set_tile_schedule": (C.c_int, [_ctx, C.c_int]),
     "rt_set_phong_gbuffer": (C.c_int, [_ctx, C.c_int]),
     "rt_phong_gbuffer": (C.c_int, [_ctx]),
+    "rt_set_rectangles": (C.c_int, [_ctx, C.c_int]),
+    "rt_rectangles": (C.c_int, [_ctx]),
     "rt_tile_schedule_state": (C.c_int, [_ctx]),
     "rt_tile_schedule_orders": (C.c_int, [_ctx]),
     "rt_set_cull_cache": (C.c_int, [_ctx, C.c_int]),
@@ -87,6 +90,10 @@ SIGNATURES = {
                                      _fp]),
     "rt_pixel_rays_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _ip, C.c_size_t, _fp, _fp]),
     "rt_occluded_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, _fp, C.c_size_t, _vp]),
+    "rt_rectangle_eval_host": (C.c_float, [_fp, _fp, _fp]),
+    "rt_trace_rays_host_ex": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, _fp, C.c_size_t, C.c_float, C.c_int,
+                                        _fp, _ip, _fp]),
+    "rt_occluded_host_ex": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, _fp, C.c_size_t, C.c_int, _vp]),
     "rt_present": (C.c_int, [_ctx, C.c_int]),
     "rt_present_device_ptr": (_vp, [_ctx]),
     "rt_bind_present": (C.c_int, [_ctx, _vp]),
@@ -116,6 +123,7 @@ SIGNATURES = {
     "rt_group_last_hip_error": (C.c_int, [_grp]),
     "rt_group_enable_pipelining": (C.c_int, [_grp, C.c_int]),
     "rt_group_set_phong_gbuffer": (C.c_int, [_grp, C.c_int]),
+    "rt_group_set_rectangles": (C.c_int, [_grp, C.c_int]),
     "rt_group_bind_frame": (C.c_int, [_grp, _vp]),
     "rt_group_frame_device_ptr": (_vp, [_grp]),
     "rt_group_upload_header": (C.c_int, [_grp, _vp, C.c_size_t]),

@@ -473,6 +473,39 @@ __device__ __forceinline__ void plane_candidate(f3 pos, f3 dir, float4 a, float4
   ind = acc ? i : ind;
 }
 
+// Rectangles (include/rt/abi.h "Rectangles"; rt_table.h rect_table).  An entry (a, b) of the plane
+// table is a rectangle when b.w != 0: a = (n, bits(index)), b = (llc, bits(offset)), its rows
+// planes[offset] = (right, dot(right, right)) and planes[offset + 1] = (up, dot(up, up)).  The rule
+// is plane_eval_ray with p0 = llc, then the hit point's two slabs: q = (pos + t * dir) - llc (one
+// multiply, one add, one subtract per component), 0 <= dot(q, right) <= |right|^2 and the same for
+// up, edges inclusive; a NaN fails a comparison (a miss).  plane_eval's -1 of the parallel case goes
+// through the slabs and comes out -1 either way.  The entry is wave-uniform at every call (a scalar
+// loop index), so the offset test is a scalar branch and the rows come through scalar loads.
+// RC = false: plane_eval, the same machine code as before.
+template <bool RC>
+__device__ __forceinline__ float planar_eval(const float4* __restrict__ planes, f3 pos, f3 dir, float4 a, float4 b) {
+  const float t = plane_eval(pos, dir, a, b);
+  if (!RC) return t;
+  const int off = __float_as_int(b.w);
+  if (off == 0) return t;  // a plane
+  const float4 r = planes[off], u = planes[off + 1];
+  const f3 q = (pos + t * dir) - xyz(b);
+  const float ar = dot(q, xyz(r)), au = dot(q, xyz(u));
+  return (ar >= 0.0f && ar <= r.w && au >= 0.0f && au <= u.w) ? t : -1.0f;
+}
+
+// plane_candidate over an entry that may be a rectangle (RC)
+template <bool RC>
+__device__ __forceinline__ void planar_candidate(const float4* __restrict__ planes, f3 pos, f3 dir, float4 a, float4 b,
+                                                 float thr, float& t, int& ind) {
+  if (!RC) return plane_candidate(pos, dir, a, b, thr, t, ind);
+  const float res = planar_eval<true>(planes, pos, dir, a, b);
+  const int i = __float_as_int(a.w);
+  const bool acc = res > thr && (t < 0.0f || res < t || (res == t && i < ind));
+  t = acc ? res : t;
+  ind = acc ? i : ind;
+}
+
 // All-sphere closest hit with the min-t update inside the hit branch and the geometry of 4
 // spheres fetched before any of them is tested (V = 2: global table read with wave-uniform
 // scalar loads; V = 0: closest_hit).  Bit-identical to closest_hit.
@@ -606,6 +639,12 @@ __device__ __forceinline__ f3 shape_normal(float4 g, int id, f3 p) {
   if (id == SHAPE_SPHERE) return normalize(p - xyz(g));
   if (id == SHAPE_PLANE) return xyz(g);
   return mk(0.0f, 0.0f, 0.0f);
+}
+// RC: the hit is a sphere, a plane or a rectangle in effect, whose normal is the stored one as a plane's
+template <bool RC>
+__device__ __forceinline__ f3 shape_normal_rc(float4 g, int id, f3 p) {
+  if (!RC) return shape_normal(g, id, p);
+  return id == SHAPE_SPHERE ? normalize(p - xyz(g)) : xyz(g);
 }
 
 }  // namespace rt

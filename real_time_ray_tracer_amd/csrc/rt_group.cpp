@@ -115,6 +115,7 @@ struct rt_group {
   std::vector<int> bounds;
   bool pipelined = false;
   bool phong_gbuf = false;  // rt_group_set_phong_gbuffer: kept across re-created strips, as pipelining is
+  bool rectangles = false;  // rt_group_set_rectangles: kept in the same way
   std::vector<rt_ctx*> ctx;
   float4* frame_own = nullptr;  // [H][W] on devices[0]
   float4* frame = nullptr;      // the bound frame (own or the caller's)
@@ -188,6 +189,7 @@ int make_strips(rt_group* g) {
     int rc = rt_create(strip_dev(g, i), &c, &g->ctx[i]);
     if (rc == RT_OK && g->pipelined) rc = rt_enable_pipelining(g->ctx[i], 1, nullptr);
     if (rc == RT_OK && g->phong_gbuf) rc = rt_set_phong_gbuffer(g->ctx[i], 1);
+    if (rc == RT_OK && g->rectangles) rc = rt_set_rectangles(g->ctx[i], 1);
     if (rc != RT_OK) {
       destroy_strips(g);
       return rc;
@@ -616,6 +618,16 @@ int rt_group_set_phong_gbuffer(rt_group* g, int on) {
   g->phong_gbuf = on != 0;
   for (auto* c : g->ctx) {
     int rc = rt_set_phong_gbuffer(c, on);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+int rt_group_set_rectangles(rt_group* g, int on) {
+  if (!g) return RT_E_INVAL;
+  g->rectangles = on != 0;
+  for (auto* c : g->ctx) {
+    int rc = rt_set_rectangles(c, on);
     if (rc != RT_OK) return rc;
   }
   return RT_OK;

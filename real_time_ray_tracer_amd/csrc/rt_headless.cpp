@@ -9,10 +9,12 @@
 // main.cpp:381-388), on the GPU as well: rt_download_rgba8_scaled / rt_group_download_rgba8_scaled.
 //
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
-//               [--scene synthetic|1|5|6] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
+//               [--scene synthetic|1|5|6|7] [--rectangles 0|1] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
 //               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH] [--pick X,Y]
 // --pick X,Y prints, after the last frame, one line `pick x y ind t nx ny nz`: the closest hit of pixel
 // (X, Y)'s primary ray (frame coordinates, row 0 = the bottom row) by rt_trace_pixels at threshold 0.
+// --rectangles 1 turns rt_set_rectangles on (rt_group_set_rectangles with --strips): rectangles are drawn,
+// e.g. the area light of --scene 7 (scene 5 with the rectangle light the reference left commented out).
 // --strips G > 1 renders the frame as G row strips through the rt_group_* entry points: strip i
 // on device devices[i % #devices] (default, without --devices: every visible device in turn,
 // starting at --device), cost-balanced with --balance ROUNDS timed plans (0: equal strips),
@@ -52,7 +54,7 @@ static void write_ppm(const char* path, const std::vector<uint8_t>& rgba, int W,
 
 // The frame as `strips` row strips over the devices in `devlist` (rt_group_*).
 static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode, int frames, int pipeline,
-                      int strips, const std::string& devlist, int device, int balance, const std::string& ppm,
+                      int rectangles, int strips, const std::string& devlist, int device, int balance, const std::string& ppm,
                       int ppm_w, int ppm_h) {
   std::vector<int> devs;
   for (size_t p = 0; p < devlist.size();) {
@@ -82,6 +84,7 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   rt_group* g = nullptr;
   check(rt_group_create(strips, sd.data(), &cfg, nullptr, &g), "rt_group_create (peer access to the first device?)");
   if (pipeline) check(rt_group_enable_pipelining(g, 1), "rt_group_enable_pipelining");
+  if (rectangles) check(rt_group_set_rectangles(g, 1), "rt_group_set_rectangles");
   // a frame that ends as a PPM is assembled as 8-bit strips (top row first), not float ones; one
   // scaled to --ppm-size is filtered from the float frame, which 8-bit strips would not assemble
   if (!ppm.empty() && ppm_w == 0) check(rt_group_enable_rgba8(g, 1, 1), "rt_group_enable_rgba8");
@@ -114,7 +117,7 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
 }
 
 int main(int argc, char** argv) {
-  int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0;
+  int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0, rectangles = 0;
   int ppm_w = 0, ppm_h = 0;  // --ppm-size (0: the frame's own size)
   bool pick = false;         // --pick X,Y: what is under that pixel after the last frame
   int pick_x = 0, pick_y = 0;
@@ -133,6 +136,7 @@ int main(int argc, char** argv) {
     else if (k == "--device") device = std::atoi(v.c_str());
     else if (k == "--ppm") ppm = v;
     else if (k == "--pipeline") pipeline = std::atoi(v.c_str());
+    else if (k == "--rectangles") rectangles = std::atoi(v.c_str());
     else if (k == "--strips") strips = std::atoi(v.c_str());
     else if (k == "--devices") devlist = v;
     else if (k == "--balance") balance = std::atoi(v.c_str());
@@ -163,12 +167,13 @@ int main(int argc, char** argv) {
   else check(rt_init_scene(header.data(), S, A, std::atoi(scene.c_str()), aspect), "rt_init_scene");
 
   rt_config cfg{W, H, S, A, RT_NUM_FRAMES, RT_RECURSION_DEPTH, 0, 0};
-  if (strips > 1) return run_strips(cfg, header, mode, frames, pipeline, strips, devlist, device, balance, ppm,
+  if (strips > 1) return run_strips(cfg, header, mode, frames, pipeline, rectangles, strips, devlist, device, balance, ppm,
                                 ppm_w, ppm_h);
   rt_ctx* ctx = nullptr;
   check(rt_create(device, &cfg, &ctx), "rt_create");
   check(rt_enable_timing(ctx, 1), "rt_enable_timing");
   if (pipeline) check(rt_enable_pipelining(ctx, 1, nullptr), "rt_enable_pipelining");
+  if (rectangles) check(rt_set_rectangles(ctx, 1), "rt_set_rectangles");
   int frame = 0;
   auto t0 = std::chrono::steady_clock::now();
   for (int k = 0; k < frames; ++k) {

@@ -200,6 +200,13 @@ int rt_init_scene(float* header, int S, int AA, int which, float aspect) {
                        {{0, 0, 0}, 2, {0.2f, 0.6f, 0.8f}, 0.4f, 0},
                        {{0, -35, 0}, 33, {0.8f, 0.6f, 0.2f}, 1.0f, 0}};
     for (int i = 0; i < 3; ++i) rt_pack_sphere(header, S, i, sp[i].c, sp[i].r, sp[i].col, sp[i].refl, sp[i].emis);
+  } else if (which == 7) {  // scene 5 with the rectangle area light the reference left commented out (src/scene.h:80-86)
+    if (S < 3) return RT_E_INVAL;
+    default_header(header, S, AA, aspect, 3);
+    const float llc[3] = {4, 6, 4}, right[3] = {0, 0, -8}, up[3] = {-8, 0, 0}, col[3] = {1.5f, 1.5f, 1.5f};
+    rt_pack_rectangle(header, S, 0, llc, right, up, col, 1.0f, 1);
+    const Sph sp[2] = {{{0, 0, 0}, 2, {0.2f, 0.6f, 0.8f}, 0.4f, 0}, {{0, -35, 0}, 33, {0.8f, 0.6f, 0.2f}, 1.0f, 0}};
+    for (int i = 0; i < 2; ++i) rt_pack_sphere(header, S, 1 + i, sp[i].c, sp[i].r, sp[i].col, sp[i].refl, sp[i].emis);
   } else if (which == 6) {  // src/scene.h:111-167
     if (S < 6) return RT_E_INVAL;
     default_header(header, S, AA, aspect, 6);

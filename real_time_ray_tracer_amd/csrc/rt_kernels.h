@@ -63,6 +63,9 @@ struct FrameParams {
   const unsigned long long* clmask;  // [1 + kMaxClusters][kClusterWords]: always-tested spheres, then members
   const float4* camrel;              // [S] (camera - centre, |camera - centre|^2 as the kernels' dot) per sphere
   int ncl;
+  int nrects;                // rectangles in effect among the plane table's nplanes entries (rt_table.h rect_table); read
+                             // by the launcher only (> 0: the RC instantiations), in the padding behind ncl, so no
+                             // other member moves
   const float4* rb;          // rand_buffer[2*spp]
   float4* out_pix;           // colour destination [band_rows][W]
   float4* nrm;               // normals_buffer slot `frame` [band_rows][W]
@@ -108,6 +111,8 @@ static_assert(offsetof(FrameParams, bg) == 160 && offsetof(FrameParams, cull_fra
               "cull_frames fills the padding in front of bg");
 static_assert(offsetof(FrameParams, phong_gbuf) == 204 && offsetof(FrameParams, clus) == 208,
               "phong_gbuf fills the padding behind nplanes");
+static_assert(offsetof(FrameParams, ncl) == 232 && offsetof(FrameParams, nrects) == 236 && offsetof(FrameParams, rb) == 240,
+              "nrects fills the padding behind ncl");
 
 // bytes of the sort frames in front of a cull table of `pools` pools (two float4 per pool)
 constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2 * sizeof(float4); }
@@ -115,9 +120,9 @@ constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2
 enum KernelId { K_AOP = 1, K_POST = 2, K_AO = 3, K_PHONG = 4, K_HYBRID = 5 };
 
 // Launch `program` (RT_PROG_* numbering) on `stream`.  Scenes with planes (p.nplanes > 0)
-// take the plane-testing instantiations; every other shape but spheres and planes is never
-// hit (eval_ray returns -1 for it, p_compute.glsl:121-138) and is skipped through the NaN
-// entries of the sphere table.  Returns hipSuccess or the launch error.
+// take the plane-testing instantiations, scenes with rectangles in effect (p.nrects > 0, counted in
+// p.nplanes too) their RC twins; every other shape is never hit (eval_ray returns -1 for it,
+// p_compute.glsl:121-138) and is skipped through the NaN entries of the sphere table.  Returns hipSuccess or the launch error.
 hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream);
 
 // Fill `table` ([ao_pool_count(p.trace_rows, p.W, p.spp)][(p.nobj + 63) / 64] u64) with the
@@ -167,7 +172,10 @@ struct QueryScene {
   float vx, vy, vz;      // vertical
   float lx, ly, lz;      // llc_minus_campos
   float cx, cy, cz;      // camera_location
+  int nrects;            // rectangles in effect among the nplanes entries (in the struct's tail padding: RayQuery's
+                         // members stay where they were)
 };
+static_assert(sizeof(QueryScene) == 80, "nrects fills QueryScene's tail padding");
 // Closest hit of n rays at threshold thr (finite, >= 0), one ray per lane: the rays (origins[i],
 // dirs[i]) ([n][3] each), or when xy is non-null the camera's rays through the pixels xy[i]
 // ([n][2] int).  Outputs, each skipped when null: t [n], ind [n], nrm [n][3], and for pixel rays

@@ -462,20 +462,24 @@ __device__ __forceinline__ unsigned long long uniform_mask(unsigned long long m)
          (unsigned)__builtin_amdgcn_readfirstlane((unsigned)m);
 }
 
-// every plane of the scene
+// every plane of the scene (RC: every entry of the plane table, rectangles in effect among them)
+template <bool RC = false>
 __device__ __forceinline__ void plane_pass(const FrameParams& P, f3 pos, f3 dir, float thr, float& t, int& ind) {
-  for (int k = 0; k < P.nplanes; ++k) plane_candidate(pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
+  for (int k = 0; k < P.nplanes; ++k)
+    planar_candidate<RC>(P.planes, pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
 }
 
 // the planes k < 64 whose bit is set in the wave-uniform mask m, and every plane k >= 64
+template <bool RC = false>
 __device__ __forceinline__ void plane_pass_masked(const FrameParams& P, unsigned long long m, f3 pos, f3 dir, float thr,
                                                   float& t, int& ind) {
   while (m) {
     const int k = __builtin_ctzll(m);
     m &= m - 1;
-    plane_candidate(pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
+    planar_candidate<RC>(P.planes, pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
   }
-  for (int k = 64; k < P.nplanes; ++k) plane_candidate(pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
+  for (int k = 64; k < P.nplanes; ++k)
+    planar_candidate<RC>(P.planes, pos, dir, P.planes[2 * k], P.planes[2 * k + 1], thr, t, ind);
 }
 
 // A plane that no camera ray of the cone can accept.  Every such ray starts at the camera, so
@@ -506,7 +510,8 @@ __device__ __forceinline__ bool plane_cone_misses(const ConeF& c, float4 a, floa
   return false;  // NaN
 }
 
-// wave-uniform mask of the planes k < 64 that the cone does not exclude
+// wave-uniform mask of the planes k < 64 that the cone does not exclude (a rectangle's entry is
+// tested as its plane: a cone that cannot reach the plane cannot reach a part of it)
 __device__ __forceinline__ unsigned long long plane_cone_mask(const FrameParams& P, const ConeF& cone, f3 cam) {
   const int k = lane_id_here();
   const bool keep = k < P.nplanes && !plane_cone_misses(cone, P.planes[2 * k], P.planes[2 * k + 1], cam);
@@ -522,7 +527,7 @@ __device__ __forceinline__ unsigned long long plane_cone_mask(const FrameParams&
 // tested from the per-frame camera-relative rows (P.camrel: camera - centre and its self dot,
 // computed on the host with the same float operations), so each test skips the three subtractions
 // and the self dot; rays from any other origin must use closest_hit / closest_hit_pf.
-template <bool PL, bool SKIP = false>
+template <bool PL, bool SKIP = false, bool RC = false>
 __device__ __forceinline__ int closest_hit_cone(const FrameParams& P, const float4* __restrict__ geo, int nobj,
                                                 const ConeF& cone, f3 dir, float thr, float& t_out,
                                                 const float4* pre0 = nullptr) {
@@ -549,7 +554,7 @@ __device__ __forceinline__ int closest_hit_cone(const FrameParams& P, const floa
     const int i = w + lane;
     word(w, i < nobj && !cone_misses_f(cone, geo[i], cam.x, cam.y, cam.z));
   }
-  if (PL) plane_pass_masked(P, plane_cone_mask(P, cone, cam), cam, dir, thr, t, ind);
+  if (PL) plane_pass_masked<RC>(P, plane_cone_mask(P, cone, cam), cam, dir, thr, t, ind);
   t_out = t;
   return ind;
 }
@@ -613,7 +618,7 @@ __device__ __forceinline__ bool shadow_cone_keeps(const ConeF& cone, bool wide, 
 }
 // PL: planes occlude too (any shape type does, p_compute.glsl:153); they are tested after the
 // spheres ("some occluder exists" does not depend on the order).
-template <bool PL>
+template <bool PL, bool RC = false>
 __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const float4* __restrict__ geo, int n, f3 light,
                                                 f3 pos, bool need, const float4* pre0 = nullptr) {
   const f3 lv = light - pos;
@@ -625,7 +630,7 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
   bool lit = true;
   if (PL)
     for (int k = 0; k < P.nplanes; ++k)
-      if (need && lit && shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) lit = false;
+      if (need && lit && shadow_occludes(planar_eval<RC>(P.planes, np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) lit = false;
   if (n <= kShadowConeMinObj) {  // small scenes: the cone costs more than it saves
     for (int k = 0; k < n; ++k) {
       if (need && lit && shadow_occludes(sphere_eval_shadow(np, l, geo[k]), l, dlen)) lit = false;
@@ -662,7 +667,7 @@ __device__ __forceinline__ bool shadow_lit_cone(const FrameParams& P, const floa
 // ---------------------------------------------------------------------------------------
 // shadow_ray over the sphere table (every lane on its own; the hybrid kernel's bounces), with
 // the planes first when the scene has some (any order: "some occluder exists")
-template <bool PL>
+template <bool PL, bool RC = false>
 __device__ __forceinline__ bool shadow_lit_sph(const FrameParams& P, const float4* __restrict__ geo, int n, f3 light,
                                                f3 pos) {
   const f3 lv = light - pos;
@@ -672,7 +677,7 @@ __device__ __forceinline__ bool shadow_lit_sph(const FrameParams& P, const float
   const double dlen = (double)len;
   if (PL)
     for (int k = 0; k < P.nplanes; ++k)
-      if (shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) return false;
+      if (shadow_occludes(planar_eval<RC>(P.planes, np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen)) return false;
   for (int i = 0; i < n; ++i)
     if (shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen)) return false;
   return true;
@@ -684,7 +689,8 @@ __device__ __forceinline__ bool shadow_lit_sph(const FrameParams& P, const float
 // the spheres).  !ALLSPH (A/B builds only): the whole shape table staged in LDS, every shape
 // tested through eval_ray's id dispatch, no culling.
 // GB: the pixel's primary hit goes to the g-buffer slot *gb as well (store_gbuf).
-template <bool ALLSPH, bool PL, bool LT, int BWX = 2, int BWY = 2, bool GB = false>
+// RC (with ALLSPH and PL): the plane table may hold rectangles in effect (rt_device.h planar_eval).
+template <bool ALLSPH, bool PL, bool LT, int BWX = 2, int BWY = 2, bool GB = false, bool RC = false>
 __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* lds, int bx, int by, const FrameDst& fd,
                                            const float4* __restrict__ gsph, const float4* __restrict__ gshp,
                                            const float4* pre0 = nullptr, const GbDst* gb = nullptr) {
@@ -702,14 +708,14 @@ __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* l
   int ind;
   if (ALLSPH) {
     const ConeF cone = wave_tile_cone<BWX, BWY>(P, bx, by);
-    ind = closest_hit_cone<PL>(P, geo, n, cone, dir, 0.0f, t, pre0);
+    ind = closest_hit_cone<PL, false, RC>(P, geo, n, cone, dir, 0.0f, t, pre0);
   } else {
     ind = closest_hit<ALLSPH>(geo, geo2, n, cam, dir, 0.0f, t);
   }
   count_work(P, active, y, 1u, active && ind != -1 ? 1u : 0u);
   const bool need = active && ind != -1;
   bool lit_w = true;
-  if (ALLSPH) lit_w = shadow_lit_cone<PL>(P, geo, n, light, cam + t * dir, need, pre0);  // every lane takes part
+  if (ALLSPH) lit_w = shadow_lit_cone<PL, RC>(P, geo, n, light, cam + t * dir, need, pre0);  // every lane takes part
   if (!active) return;
   float r, g, b;
   if (ind == -1) {
@@ -719,7 +725,7 @@ __device__ __forceinline__ void phong_tile(const FrameParams& P, const float4* l
     f3 curr = cam + t * dir;
     bool lit = ALLSPH ? lit_w : shadow_lit<ALLSPH>(geo, geo2, n, light, curr);
     int id = (ALLSPH && !PL) ? SHAPE_SPHERE : __float_as_int(geo2[ind].w);
-    f3 nn = shape_normal(tab[ind], id, curr);
+    f3 nn = shape_normal_rc<RC>(tab[ind], id, curr);
     if (GB) store_gbuf(P, *gb, x, y, true, nn, t);
     float4 c = col[ind];
     if (lit) {
@@ -796,6 +802,29 @@ __global__ __launch_bounds__(kBlock) void phong_gbuf_kernel(const float4* __rest
   }
 }
 
+// phong_kernel<true, true, false, MF> (GB: phong_gbuf_kernel<true, MF>) over a plane table with
+// rectangles in effect (the RC tile): entry points of their own, so the kernels above keep their
+// names and code.
+template <bool MF, bool GB>
+__global__ __launch_bounds__(kBlock) void phong_rc_kernel(const float4* __restrict__ gsph, const float4* __restrict__ gshp,
+                                                          FrameParams P) {
+  if constexpr (!MF) {
+    const float4 g0 = gsph[threadIdx.x & 63];  // as phong_kernel
+    const GbDst gb = frame_gb<false>(P, 0);
+    phong_tile<true, true, false, 2, 2, GB, true>(P, nullptr, blockIdx.x, blockIdx.y, frame_dst<false>(P, 0), gsph, gshp,
+                                                  &g0, GB ? &gb : nullptr);
+    return;
+  }
+  int j0;
+  const int nj = block_frames<kPhongFramesPerBlock>(P, j0);
+#pragma unroll 1
+  for (int j = 0; j < nj; ++j) {
+    const GbDst gb = frame_gb<true>(P, j0 + j);
+    phong_tile<true, true, false, 2, 2, GB, true>(P, nullptr, blockIdx.x, blockIdx.y, frame_dst(P, j0 + j), gsph, gshp,
+                                                  nullptr, GB ? &gb : nullptr);
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // mode 4 — h_compute.glsl:186-321
 // ---------------------------------------------------------------------------------------
@@ -807,7 +836,7 @@ __global__ __launch_bounds__(kBlock) void phong_gbuf_kernel(const float4* __rest
 // segment's shadow ray ("some occluder exists" is order-free, p_compute.glsl:145-166).  With
 // more than 32 live paths every lane traces its own.  Returns (for the owner lanes) t, ind, lit.
 // Must be called by every lane of the wave; perm: this wave's 64-int LDS slice.
-template <bool PL>
+template <bool PL, bool RC = false>
 __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4* __restrict__ geo, int n, f3 light,
                                              bool live, f3 pos, f3 dir, int* perm, float& t_out, int& ind_out,
                                              bool& lit_out) {
@@ -820,8 +849,8 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
     bool lit = true;
     if (live) {
       ind = closest_hit_pf(geo, n, pos, dir, 0.001f, t);
-      if (PL) plane_pass(P, pos, dir, 0.001f, t, ind);
-      if (ind != -1) lit = shadow_lit_sph<PL>(P, geo, n, light, pos + t * dir);
+      if (PL) plane_pass<RC>(P, pos, dir, 0.001f, t, ind);
+      if (ind != -1) lit = shadow_lit_sph<PL, RC>(P, geo, n, light, pos + t * dir);
     }
     t_out = t;
     ind_out = ind;
@@ -851,7 +880,7 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
     t = take ? tb : t;
     ind = take ? ib : ind;
   }
-  if (PL && act) plane_pass(P, o, d, 0.001f, t, ind);  // same planes, same result on every group lane
+  if (PL && act) plane_pass<RC>(P, o, d, 0.001f, t, ind);  // same planes, same result on every group lane
   // the segment's shadow ray, split the same way (the owner's hit point, same float ops)
   bool occ = false;
   if (act && ind != -1) {
@@ -863,7 +892,7 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
     const double dlen = (double)len;
     if (PL)
       for (int k = pl; k < P.nplanes && !occ; k += G)
-        occ = shadow_occludes(plane_eval(np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen);
+        occ = shadow_occludes(planar_eval<RC>(P.planes, np, l, P.planes[2 * k], P.planes[2 * k + 1]), l, dlen);
     for (int i = pl; i < n && !occ; i += G) occ = shadow_occludes(sphere_eval_shadow(np, l, geo[i]), l, dlen);
   }
   unsigned oc = occ ? 1u : 0u;
@@ -878,7 +907,8 @@ __device__ __forceinline__ void bounce_round(const FrameParams& P, const float4*
 // 3 = primary cull only, 5 = no bounce segments, 6 = bounces without the split rounds
 // GB: segment 0's hit goes to the g-buffer slot *gb as well (store_gbuf), there and then, so that
 // neither t0 nor the normal stays live across the bounce rounds.
-template <bool ALLSPH, bool PL, bool LT, int ABL = 0, int BWX = 2, int BWY = 2, bool GB = false>
+// RC (with ALLSPH and PL): the plane table may hold rectangles in effect, as in phong_tile.
+template <bool ALLSPH, bool PL, bool LT, int ABL = 0, int BWX = 2, int BWY = 2, bool GB = false, bool RC = false>
 __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* lds, int* perm, int bx, int by,
                                             const FrameDst& fd, const float4* __restrict__ gsph,
                                             const float4* __restrict__ gshp, const float4* pre0 = nullptr,
@@ -915,7 +945,7 @@ __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* 
       float4 att = ABL == 9 ? make_float4(0.5f, 0.5f, 0.5f, 0.0f) : col[ind];
       f3 curr = pos + t * dir;
       int id = (ALLSPH && !PL) ? SHAPE_SPHERE : __float_as_int(geo2[ind].w);
-      f3 nn = ABL == 9 ? normalize(curr) : shape_normal(tab[ind], id, curr);
+      f3 nn = ABL == 9 ? normalize(curr) : shape_normal_rc<RC>(tab[ind], id, curr);
       if (GB && seg == 0 && active) store_gbuf(P, *gb, x, y, true, nn, t);
       if (lit) {
         f3 l = normalize(light - curr);
@@ -955,8 +985,8 @@ __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* 
     int ind0 = -1;
     bool lit0 = true;
     const ConeF cone = wave_tile_cone<BWX, BWY>(P, bx, by);
-    if (ABL != 2) ind0 = closest_hit_cone<PL, ABL == 3>(P, geo, n, cone, dir, 0.001f, t0, pre0);
-    if (ABL == 0 || ABL >= 4) lit0 = shadow_lit_cone<PL>(P, geo, n, light, pos + t0 * dir, active && ind0 != -1, pre0);  // every lane takes part
+    if (ABL != 2) ind0 = closest_hit_cone<PL, ABL == 3, RC>(P, geo, n, cone, dir, 0.001f, t0, pre0);
+    if (ABL == 0 || ABL >= 4) lit0 = shadow_lit_cone<PL, RC>(P, geo, n, light, pos + t0 * dir, active && ind0 != -1, pre0);  // every lane takes part
     bool live = active && !segment(0, t0, ind0, lit0);
     // segments 1 .. D-1: bounce rounds with the whole wave
     int rounds = 0;  // wave-uniform: the wave's cost beyond its camera rays (tile schedule)
@@ -969,11 +999,11 @@ __device__ __forceinline__ void hybrid_tile(const FrameParams& P, const float4* 
       if (ABL == 6) {
         if (live) {
           ind = closest_hit_pf(geo, n, pos, dir, 0.001f, t);
-          if (PL) plane_pass(P, pos, dir, 0.001f, t, ind);
-          if (ind != -1) lit = shadow_lit_sph<PL>(P, geo, n, light, pos + t * dir);
+          if (PL) plane_pass<RC>(P, pos, dir, 0.001f, t, ind);
+          if (ind != -1) lit = shadow_lit_sph<PL, RC>(P, geo, n, light, pos + t * dir);
         }
       } else {
-        bounce_round<PL>(P, geo, n, light, live, pos, dir, perm, t, ind, lit);
+        bounce_round<PL, RC>(P, geo, n, light, live, pos, dir, perm, t, ind, lit);
       }
       if (live) live = !segment(seg, t, ind, lit);
     }
@@ -1066,6 +1096,29 @@ __global__ __launch_bounds__(64 * BWX * BWY) void hybrid_gbuf_kernel(const unsig
                                                   frame_dst<MF>(P, blockIdx.z), gsph, gshp, MF ? nullptr : &g0, &gb);
 }
 
+// hybrid_kernel<true, true, false, 0, BWX, BWY, MF> (GB: hybrid_gbuf_kernel<true, BWX, BWY, MF>) over a
+// plane table with rectangles in effect (the RC tile); an entry point of its own, as phong_rc_kernel is.
+template <int BWX, int BWY, bool MF, bool GB>
+__global__ __launch_bounds__(64 * BWX * BWY) void hybrid_rc_kernel(const unsigned* __restrict__ tord,
+                                                                   const float4* __restrict__ gsph,
+                                                                   const float4* __restrict__ gshp, unsigned gx,
+                                                                   FrameParams P) {
+  static_assert(kHybridFramesPerBlock == 1, "one frame per block (hybrid_kernel's loop-free form)");
+  __shared__ int hperm[64 * BWX * BWY];
+  float4 g0;
+  if (!MF) g0 = gsph[threadIdx.x & 63];  // as hybrid_kernel
+  unsigned bx = blockIdx.x, by = blockIdx.y;
+  if (tord) {
+    const unsigned t = tord[blockIdx.x + blockIdx.y * gx];
+    bx = t & 0xffffu;
+    by = t >> 16;
+  }
+  const GbDst gb = frame_gb<MF>(P, blockIdx.z);
+  hybrid_tile<true, true, false, 0, BWX, BWY, GB, true>(P, nullptr, hperm + 64 * (threadIdx.x >> 6), bx, by,
+                                                        frame_dst<MF>(P, blockIdx.z), gsph, gshp, MF ? nullptr : &g0,
+                                                        GB ? &gb : nullptr);
+}
+
 // ---------------------------------------------------------------------------------------
 // modes 1/2 pass 1 — ao_compute.glsl:143-339 (aop_compute.glsl:141-336)
 // lane = (pixel, sample); ppb = blockDim / spp pixels per block, consecutive in a row.
@@ -1098,6 +1151,7 @@ struct AoConfig {
   static constexpr int SPPC = 0;       // spp as a constant (0: P.spp): constant LDS offsets and it / spp, fewer scalars
   static constexpr int DC = 0;         // the depth as a constant (0: P.D)
   static constexpr bool PL = false;    // the scene has planes: tested after the spheres of every segment, culled against the pool cone
+  static constexpr bool RC = false;    // with PL: the plane table may hold rectangles in effect (rt_device.h planar_eval)
   static constexpr bool CLON = false;  // launched only with clusters (P.ncl > 0): the rounds' plain full scan is not compiled
   static constexpr bool CNT = true;    // the work counters (false: compiled out, timed launches pass none)
   static constexpr bool MF = false;    // frame blockIdx.y of a multi-frame mode-2 launch: its own rand_buffer and slots (FrameParams::mf_rb)
@@ -1137,6 +1191,7 @@ enum : unsigned {
   AO_CNT = 16,   // AoConfig::CNT
   AO_MF = 32,    // AoConfig::MF
   AO_CULLC = 64, // AoConfig::CULLC
+  AO_RC = 128,   // AoConfig::RC (with AO_PL)
 };
 // The forms that key the sort on the pool's frame: sorted and cached, not the counter forms (their
 // work counters stay those of the uncached launch, whose key is the octant), never with planes.
@@ -1147,6 +1202,7 @@ constexpr bool ao_sorts_by_frame(unsigned flags) {
 template <int SPPC_, int DC_, unsigned FLAGS>
 struct AoProd : AoConfig {
   static constexpr int SPPC = SPPC_, DC = DC_;
+  static constexpr bool RC = FLAGS & AO_RC;
   static constexpr bool PL = FLAGS & AO_PL, CLON = FLAGS & AO_CLON, SORT = FLAGS & AO_SORT, PTW = FLAGS & AO_WIDE,
                         CNT = FLAGS & AO_CNT, MF = FLAGS & AO_MF, CULLC = FLAGS & AO_CULLC,
                         NSORT = ao_sorts_by_frame(FLAGS);
@@ -1213,6 +1269,8 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
   constexpr bool PL = C::PL, CLON = C::CLON, CNT = C::CNT, MF = C::MF, LAZY = C::LAZY, TAIL = C::TAIL, B1 = C::B1,
                  PT = C::PT, PTW = C::PTW, SORT = C::SORT, CULLC = C::CULLC;
   static_assert(!CULLC || !PL, "the cull table holds the spheres' masks only");
+  constexpr bool RC = C::RC;
+  static_assert(!RC || PL, "rectangles are entries of the plane table");
   constexpr bool NSORT = C::NSORT;
   static_assert(!NSORT || (CULLC && SORT), "the sort frames come with the cull table");
   __builtin_amdgcn_s_setprio(1);  // the pool's start at issue priority 1, back to 0 after the primary cull
@@ -1463,7 +1521,8 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
         f3 nn;
         if (PL) {  // ao_compute.glsl:211-218: the stored normal of a plane
           const float4 gi = P.shapes[ind];
-          nn = __float_as_int(P.shapes[P.S + ind].w) == SHAPE_PLANE ? xyz(gi) : normalize(curr - xyz(gi));
+          const int id = __float_as_int(P.shapes[P.S + ind].w);  // (RC: a rectangle's stored normal, as a plane's)
+          nn = (RC ? id != SHAPE_SPHERE : id == SHAPE_PLANE) ? xyz(gi) : normalize(curr - xyz(gi));
         } else {
           nn = normalize(curr - xyz(gc));
         }
@@ -1588,7 +1647,7 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
           }
         }
       }
-      if (PL) plane_pass_masked(P, pmask, bpos, bdir, 0.0001f, t, ind);
+      if (PL) plane_pass_masked<RC>(P, pmask, bpos, bdir, 0.0001f, t, ind);
       ++nseg;
       // (every hit, emissive or not: only non-emissive hits use it, but waiting for the hit's flags
       // first cost a memory round trip, and a wave with any non-emissive hit computes it anyway)
@@ -1721,7 +1780,7 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
         __builtin_amdgcn_s_setprio(0);
         if (ABL == 7) { tsec[4] += 1; tsec[5] += (unsigned long long)__popcll(lm1); }
         if (live) {
-          if (PL) plane_pass(P, bpos, bdir, 0.0001f, t, ind);
+          if (PL) plane_pass<RC>(P, bpos, bdir, 0.0001f, t, ind);
           ++nseg;
           live = shade(ind, t, bpos, bdir, bhemi, br, bg, bb, D - 1, bitem, false);
         }
@@ -1978,7 +2037,7 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
       int ii = __shfl(ind, rk * G);
       if (!(use_cl && G <= kClusterTailMaxG)) exec_tests += (unsigned long long)((nobj + G - 1) / G);
       if (has) {
-        if (PL) plane_pass(P, pos, dir, 0.0001f, tt, ii);
+        if (PL) plane_pass<RC>(P, pos, dir, 0.0001f, tt, ii);
         ++nseg;
         has = shade(ii, tt, pos, dir, hemi, rr, rg, rb, depth, item, false);
         depth -= 1;
@@ -2077,7 +2136,7 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
         }
       }
       if (has) {
-        if (PL) plane_pass(P, pos, dir, 0.0001f, t, ind);
+        if (PL) plane_pass<RC>(P, pos, dir, 0.0001f, t, ind);
         ++nseg;
         has = shade(ind, t, pos, dir, hemi, rr, rg, rb, depth, item, false);
         depth -= 1;
@@ -2085,7 +2144,7 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
     } else if (has) {
       float t;
       int ind = closest_hit_pf(geo, nobj, pos, dir, 0.0001f, t);  // 4-sphere scalar groups (pf2: +0.9%)
-      if (PL) plane_pass(P, pos, dir, 0.0001f, t, ind);
+      if (PL) plane_pass<RC>(P, pos, dir, 0.0001f, t, ind);
       if (ABL == 1) {  // timing ablation: the bounce tests twice
         float z, t2;
         asm volatile("v_mov_b32 %0, 0" : "=v"(z));
@@ -2709,6 +2768,12 @@ constexpr AoChoice ao_select(int spp, int D, int ncl, int nobj, int nplanes, boo
                       (nobj > kTailMaxObj ? AO_WIDE : 0u) | (multi_frame ? AO_MF : counters ? AO_CNT : 0u) |
                       (cull_table && !pl ? AO_CULLC : 0u)};
 }
+// Rectangles in effect (nrects > 0 of the nplanes entries): the plane scene's choice with AO_RC.
+constexpr AoChoice ao_select(int spp, int D, int ncl, int nobj, int nplanes, int nrects, bool counters, bool multi_frame,
+                             bool cull_table) {
+  const AoChoice c = ao_select(spp, D, ncl, nobj, nplanes, counters, multi_frame, cull_table);
+  return AoChoice{c.sppc, c.dc, c.flags | (nplanes > 0 && nrects > 0 ? AO_RC : 0u)};
+}
 // The dispatch's regression test (derived from the launcher this function replaced).  Arguments:
 // spp, D, ncl, nobj, nplanes, counters, multi-frame, cull table.
 constexpr unsigned kSortBit = RT_B1_SORT ? AO_SORT : 0u;
@@ -2757,6 +2822,16 @@ static_assert(!ao_sorts_by_frame(ao_select(16, 20, 9, 65, 1, false, false, true)
 static_assert(ao_select(16, 20, 9, 65, 1, false, false, true) == AoChoice{16, 0, AO_PL}, "p: never cached");
 static_assert(ao_select(4, 20, 0, 10, 1, false, false, true) == AoChoice{4, 0, AO_PL}, "ref: never cached");
 
+// rectangles: spp, D, ncl, nobj, nplanes, nrects, counters, multi-frame, cull table; the plane rows with AO_RC,
+// never cached, never sorted; no rectangle in effect: the choice above
+static_assert(ao_select(16, 20, 9, 65, 1, 1, false, false, false) == AoChoice{16, 0, AO_PL | AO_RC}, "p, ground a rectangle");
+static_assert(ao_select(4, 20, 0, 10, 2, 1, false, false, true) == AoChoice{4, 0, AO_PL | AO_RC}, "rectangles: never cached");
+static_assert(ao_select(3, 20, 0, 10, 1, 1, true, false, false) == AoChoice{0, 0, AO_PL | AO_RC | AO_CNT}, "rectangles, counters");
+static_assert(ao_select(16, 20, 0, 10, 1, 1, false, true, false) == AoChoice{16, 0, AO_PL | AO_RC | AO_MF}, "rectangles, multi-frame");
+static_assert(ao_select(64, 20, 8, 200, 2, 2, false, false, false) == AoChoice{0, 0, AO_PL | AO_RC | AO_WIDE}, "rectangles, wide");
+static_assert(ao_select(16, 20, 8, 64, 0, 0, false, false, true) == ao_select(16, 20, 8, 64, 0, false, false, true), "no rectangle");
+static_assert(ao_select(16, 20, 9, 65, 1, 0, false, false, false) == ao_select(16, 20, 9, 65, 1, false, false, false), "planes only");
+
 // Launch ao_batch_kernel<C> over `pools` pools: the LDS rows after the layout hold the sphere
 // table (C::PTW: one 64-sphere word of pre-test rows)
 template <class C>
@@ -2786,7 +2861,13 @@ inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream,
 }
 template <unsigned SORT>  // 0 or AO_SORT
 inline void launch_ao_choice(const AoChoice& c, long long pools, hipStream_t stream, const FrameParams& q) {
-  if (c.flags & AO_PL) {
+  if (c.flags & AO_RC) {  // (with AO_PL)
+    if constexpr (SORT == 0) {
+      if (c.sppc == 16) launch_ao_shape<16, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
+      else if (c.sppc == 4) launch_ao_shape<4, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
+      else launch_ao_shape<0, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
+    }
+  } else if (c.flags & AO_PL) {
     if constexpr (SORT == 0) {
       if (c.sppc == 16) launch_ao_shape<16, 0, AO_PL>(c.flags, pools, stream, q);
       else if (c.sppc == 4) launch_ao_shape<4, 0, AO_PL>(c.flags, pools, stream, q);
@@ -3095,6 +3176,75 @@ __global__ __launch_bounds__(kBlock) void occluded_kernel(QueryScene sc, const f
   out[i] = lit ? 0 : 1;
 }
 
+// Rectangles in effect (sc.nrects > 0; include/rt/abi.h "Rectangles"): the spheres over the sphere
+// table (query_closest<false>'s scan), then every entry of the plane table, planes and rectangles,
+// merged by planar_candidate's (t, index) rule: the result of eval_ray's ascending scan whatever the
+// visiting order, as in the frame kernels.
+__device__ __forceinline__ int query_closest_rc(const QueryScene& sc, f3 pos, f3 dir, float thr, float& t_out) {
+  float t;
+  int ind = query_closest<false>(sc, pos, dir, thr, t);
+  const float4* __restrict__ planes = sc.shapes + plane_table(sc.S);
+  for (int k = 0; k < sc.nplanes; ++k)
+    planar_candidate<true>(planes, pos, dir, planes[2 * k], planes[2 * k + 1], thr, t, ind);
+  t_out = t;
+  return ind;
+}
+
+// ray_query_kernel<true, PIX> over a plane table with rectangles in effect; an entry point of its own,
+// so the kernels above keep their names and code.
+template <bool PIX>
+__global__ __launch_bounds__(kBlock) void ray_query_rc_kernel(RayQuery Q) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= Q.n) return;
+  f3 o, d;
+  if (PIX) {
+    const int x = Q.xy[2 * i], y = Q.xy[2 * i + 1];
+    o = mk(Q.sc.cx, Q.sc.cy, Q.sc.cz);
+    d = primary_dir(Q.sc, (float)x / Q.sc.fW, (float)y / Q.sc.fH);
+  } else {
+    o = mk(Q.origins[3 * i], Q.origins[3 * i + 1], Q.origins[3 * i + 2]);
+    d = mk(Q.dirs[3 * i], Q.dirs[3 * i + 1], Q.dirs[3 * i + 2]);
+  }
+  float t;
+  const int ind = query_closest_rc(Q.sc, o, d, Q.thr, t);
+  if (Q.t) Q.t[i] = t;
+  if (Q.ind) Q.ind[i] = ind;
+  if (Q.nrm) {
+    f3 n = mk(0.0f, 0.0f, 0.0f);
+    if (ind >= 0) n = shape_normal_rc<true>(Q.sc.shapes[ind], __float_as_int(Q.sc.shapes[Q.sc.S + ind].w), o + t * d);
+    Q.nrm[3 * i] = n.x;
+    Q.nrm[3 * i + 1] = n.y;
+    Q.nrm[3 * i + 2] = n.z;
+  }
+  if (PIX && Q.dir_out) {
+    Q.dir_out[3 * i] = d.x;
+    Q.dir_out[3 * i + 1] = d.y;
+    Q.dir_out[3 * i + 2] = d.z;
+  }
+}
+
+// occluded_kernel<true> over a plane table with rectangles in effect: shadow_ray with the plane
+// table's entries first, then the sphere table ("some occluder exists" does not depend on the order).
+__global__ __launch_bounds__(kBlock) void occluded_rc_kernel(QueryScene sc, const float* __restrict__ from,
+                                                             const float* __restrict__ to, size_t n,
+                                                             unsigned char* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const f3 pos = mk(from[3 * i], from[3 * i + 1], from[3 * i + 2]);
+  const f3 lv = mk(to[3 * i], to[3 * i + 1], to[3 * i + 2]) - pos;
+  const f3 l = normalize(lv);
+  const float len = sqrtf(dot(lv, lv));
+  const f3 np = pos + 0.01f * l;
+  const double dlen = (double)len;
+  const float4* __restrict__ planes = sc.shapes + plane_table(sc.S);
+  const float4* __restrict__ sph = sc.shapes + sphere_table(sc.S);
+  bool occ = false;
+  for (int k = 0; k < sc.nplanes && !occ; ++k)
+    occ = shadow_occludes(planar_eval<true>(planes, np, l, planes[2 * k], planes[2 * k + 1]), l, dlen);
+  for (int k = 0; k < sc.nobj && !occ; ++k) occ = shadow_occludes(sphere_eval_shadow(np, l, sph[k]), l, dlen);
+  out[i] = occ ? 1 : 0;
+}
+
 constexpr size_t kQueryMaxRays = (size_t)1 << 28;  // RT_QUERY_MAX_RAYS: the grid's x stays below 2^31
 
 hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream) {
@@ -3102,6 +3252,11 @@ hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream) {
   if (q.n > kQueryMaxRays || !q.sc.shapes || (!q.xy && (!q.origins || !q.dirs))) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((q.n + kBlock - 1) / kBlock));
   const bool pl = q.sc.nplanes > 0;
+  if (pl && q.sc.nrects > 0) {  // rectangles in effect: the RC twins
+    if (q.xy) hipLaunchKernelGGL(ray_query_rc_kernel<true>, grid, dim3(kBlock), 0, stream, q);
+    else hipLaunchKernelGGL(ray_query_rc_kernel<false>, grid, dim3(kBlock), 0, stream, q);
+    return hipGetLastError();
+  }
   if (q.xy) {
     if (pl) hipLaunchKernelGGL((ray_query_kernel<true, true>), grid, dim3(kBlock), 0, stream, q);
     else hipLaunchKernelGGL((ray_query_kernel<false, true>), grid, dim3(kBlock), 0, stream, q);
@@ -3117,7 +3272,8 @@ hipError_t launch_occluded(const QueryScene& sc, const float* from, const float*
   if (n == 0) return hipSuccess;
   if (n > kQueryMaxRays || !sc.shapes || !from || !to || !out) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  if (sc.nplanes > 0) hipLaunchKernelGGL(occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  if (sc.nplanes > 0 && sc.nrects > 0) hipLaunchKernelGGL(occluded_rc_kernel, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  else if (sc.nplanes > 0) hipLaunchKernelGGL(occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   else hipLaunchKernelGGL(occluded_kernel<false>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   return hipGetLastError();
 }
@@ -3163,8 +3319,8 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const long long npix = (long long)p.trace_rows * p.W;
     const int TP = kPool / p.spp > 0 ? kPool / p.spp : 1;
     const long long pools = (npix + TP - 1) / TP;
-    const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.counters || p.row_counters, p.mf_n > 0,
-                                 q.cull != nullptr);
+    const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.nrects, p.counters || p.row_counters,
+                                 p.mf_n > 0, q.cull != nullptr);
     // (kSortBit: a build with RT_B1_SORT=0 never selects the sort and compiles no SORT instantiation)
     if (c.flags & AO_SORT) launch_ao_choice<kSortBit>(c, pools, stream, q);
     else launch_ao_choice<0>(c, pools, stream, q);
@@ -3180,6 +3336,21 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
   // survivor tests, vector loads for the hit's material), not staged in LDS per block (the LT
   // instantiations, A/B tools library only)
   const bool mf = p.mf_n > 0;  // multi-frame launch; single-frame ones take the MF = false kernels
+  if (pl && p.nrects > 0 && (program == K_PHONG || program == K_HYBRID)) {  // rectangles in effect: the RC twins
+    const bool gb = p.phong_gbuf != 0;
+    if (program == K_PHONG) {
+      if (mf && gb) hipLaunchKernelGGL((phong_rc_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (mf) hipLaunchKernelGGL((phong_rc_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (gb) hipLaunchKernelGGL((phong_rc_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else hipLaunchKernelGGL((phong_rc_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+    } else {
+      if (mf && gb) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, true, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (mf) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, true, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (gb) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, false, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, false, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+    }
+    return hipGetLastError();
+  }
   if (p.phong_gbuf && (program == K_PHONG || program == K_HYBRID)) {  // rt_set_phong_gbuffer: the GB instantiations
     if (program == K_PHONG) {
       if (pl && mf) hipLaunchKernelGGL((phong_gbuf_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);

@@ -124,7 +124,15 @@ int build_clusters(const Row* sph, int nobj, Row* ctab, unsigned long long* cmas
 }
 
 int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& nplanes, int& ncl) {
+  int nrects = 0;
+  return pack_header(cfg, h, tab, nobj, nplanes, ncl, 0, nrects);
+}
+
+int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& nplanes, int& ncl, int flags,
+                int& nrects) {
   const int S = cfg.num_shapes, spp = cfg.spp;
+  const bool rects = (flags & RT_SCENE_RECTANGLES) != 0;
+  int nr = 0;
   nobj = header_nobj(h, S);
   if (nobj < 0) return RT_E_INVAL;
   const float* sh = h + rt_off_shapes() / 4;
@@ -152,8 +160,25 @@ int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& 
       pln[2 * np] = a;
       pln[2 * np + 1] = Row{s[12], s[13], s[14], 0.0f};
       ++np;
+    } else if (rects && i < nobj && id == RT_SHAPE_RECTANGLE) {
+      // a rectangle in effect: (n, bits(index)), (llc, bits(offset of its rows from the plane table));
+      // the rows: (right, dot(right, right)), (up, dot(up, up)), the kernels' fused chain
+      Row a = Row{s[0], s[1], s[2], 0.0f};
+      std::memcpy(&a.w, &i, 4);
+      Row b = Row{s[12], s[13], s[14], 0.0f};
+      const int off = (int)(rect_table(Sc, spp) - plane_table(Sc)) + 2 * nr;
+      std::memcpy(&b.w, &off, 4);
+      pln[2 * np] = a;
+      pln[2 * np + 1] = b;
+      ++np;
+      Row* rr = tab + rect_table(Sc, spp) + 2 * nr;
+      rr[0] = Row{s[8], s[9], s[10], std::fmaf(s[10], s[10], std::fmaf(s[9], s[9], s[8] * s[8]))};
+      rr[1] = Row{s[4], s[5], s[6], std::fmaf(s[6], s[6], std::fmaf(s[5], s[5], s[4] * s[4]))};
+      ++nr;
     }
   }
+  if (rects) std::memset((void*)(tab + rect_table(Sc, spp) + 2 * nr), 0, (size_t)(2 * Sc - 2 * nr) * sizeof(Row));
+  nrects = nr;
   // the padding rows; the colour table's row -1 is the background (table_stride)
   for (int k = 0; k < 4; ++k) tab[(size_t)k * Sc + Sc - 1] = Row{0.0f, 0.0f, 0.0f, 0.0f};
   tab[4 * (size_t)Sc + Sc - 1] = Row{qnan, qnan, qnan, qnan};  // sphere table: never accepted

@@ -29,6 +29,13 @@ int header_nobj(const float* h, int S);
 // Validate a header and pack it into the device table layout (rt::table_vec4 rows at `tab`:
 // shape tables, sphere table, plane table, clusters, rand_buffer); sets nobj / nplanes / ncl.
 int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& nplanes, int& ncl);
+// The same with flags (RT_SCENE_RECTANGLES): the rectangles among [0, nobj) enter the plane table
+// with the planes, ascending index, and their rows go to the appended region (rt_table.h
+// rect_table); `tab` then holds rt::table_vec4_rect rows, the region's unused rows zero.  nplanes
+// counts planes and rectangles, nrects the rectangles.  flags = 0 is the form above: nothing beyond
+// rt::table_vec4 is read or written.
+int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& nplanes, int& ncl, int flags,
+                int& nrects);
 
 // Bounce-ray clusters of the sphere table `sph` (see rt_plan.cpp); returns the cluster count.
 int build_clusters(const Row* sph, int nobj, Row* ctab, unsigned long long* cmask);

@@ -4,6 +4,7 @@
 // the float semantics are the ones oracle/rt_oracle.h states.
 //
 //   eval_ray, sphere_eval_ray, plane_eval_ray   p_compute.glsl:77-138
+//   the rectangle rule (flags RT_SCENE_RECTANGLES) include/rt/abi.h "Rectangles"
 //   the closest-hit loop                        p_compute.glsl:177-188 (h_ 199-210, ao_ 183-194)
 //   the primary ray                             p_compute.glsl:233-235
 //   shadow_ray                                  p_compute.glsl:145-166
@@ -50,11 +51,25 @@ float plane_eval(V3 pos, V3 dir, const float* n4, const float* p04) {
   return dot(n, sub(V3{p04[0], p04[1], p04[2]}, pos)) / denom;
 }
 
+// The rectangle rule (include/rt/abi.h "Rectangles") on row sh as loadShapeBuffer packs it
+// (src/main.cpp:444-467): n = [0].xyz, up = [1].xyz, right = [2].xyz, llc = [3].xyz.  plane_eval_ray
+// with p0 = llc, then the hit point's two slabs; edges inclusive, a NaN fails a comparison.
+float rectangle_eval(V3 pos, V3 dir, const float* sh) {
+  const V3 n{sh[0], sh[1], sh[2]}, up{sh[4], sh[5], sh[6]}, right{sh[8], sh[9], sh[10]}, llc{sh[12], sh[13], sh[14]};
+  const float den = dot(n, dir);
+  if (den < 0.001f && den > -0.001f) return -1.0f;
+  const float t = dot(n, sub(llc, pos)) / den;
+  const V3 q = sub(add(pos, scale(t, dir)), llc);  // one multiply, one add, one subtract per component
+  const float a = dot(q, right), b = dot(q, up);
+  return (a >= 0.0f && a <= dot(right, right) && b >= 0.0f && b <= dot(up, up)) ? t : -1.0f;
+}
+
 // a header checked against its configuration
 struct Scene {
   const float* hdr;
   const float* shapes;  // simple_shapes[S][5] vec4
   int nobj;
+  bool rects;  // RT_SCENE_RECTANGLES: shape id 3 follows rectangle_eval (else it is never hit)
 };
 
 // int(simple_shapes[i][4].w), 0 for a value no int holds (as the device table's packing)
@@ -68,10 +83,13 @@ float eval_ray(const Scene& s, V3 pos, V3 dir, int i) {
   const int id = shape_id(s, i);
   if (id == RT_SHAPE_SPHERE) return sphere_eval(pos, dir, sh);
   if (id == RT_SHAPE_PLANE) return plane_eval(pos, dir, sh, sh + 12);
+  if (id == RT_SHAPE_RECTANGLE && s.rects) return rectangle_eval(pos, dir, sh);
   return -1.0f;
 }
 
-int open_scene(const rt_config* cfg, const void* header, size_t header_bytes, Scene& s) {
+int open_scene(const rt_config* cfg, const void* header, size_t header_bytes, int flags, Scene& s) {
+  if ((flags & ~RT_SCENE_RECTANGLES) != 0) return RT_E_INVAL;
+  s.rects = (flags & RT_SCENE_RECTANGLES) != 0;
   if (!cfg || !header || cfg->num_shapes < 0 || cfg->spp <= 0 ||
       header_bytes != rt_header_bytes(cfg->num_shapes, cfg->spp))
     return RT_E_INVAL;
@@ -89,10 +107,21 @@ bool thr_ok(float thr) { return thr >= 0.0f && thr <= 3.402823466e+38f; }  // fi
 
 extern "C" {
 
+float rt_rectangle_eval_host(const float shape[20], const float pos[3], const float dir[3]) {
+  if (!shape || !pos || !dir) return -1.0f;
+  return rectangle_eval(V3{pos[0], pos[1], pos[2]}, V3{dir[0], dir[1], dir[2]}, shape);
+}
+
 int rt_trace_rays_host(const rt_config* cfg, const void* header, size_t header_bytes, const float* origins,
                        const float* dirs, size_t n, float thr, float* t_out, int32_t* ind_out, float* normals) {
+  return rt_trace_rays_host_ex(cfg, header, header_bytes, origins, dirs, n, thr, 0, t_out, ind_out, normals);
+}
+
+int rt_trace_rays_host_ex(const rt_config* cfg, const void* header, size_t header_bytes, const float* origins,
+                          const float* dirs, size_t n, float thr, int flags, float* t_out, int32_t* ind_out,
+                          float* normals) {
   Scene s;
-  int rc = open_scene(cfg, header, header_bytes, s);
+  int rc = open_scene(cfg, header, header_bytes, flags, s);
   if (rc != RT_OK) return rc;
   if (n > RT_QUERY_MAX_RAYS || !thr_ok(thr)) return RT_E_INVAL;
   if (n == 0) return RT_OK;
@@ -129,7 +158,7 @@ int rt_trace_rays_host(const rt_config* cfg, const void* header, size_t header_b
 int rt_pixel_rays_host(const rt_config* cfg, const void* header, size_t header_bytes, const int32_t* xy, size_t n,
                        float* origins, float* dirs) {
   Scene s;
-  int rc = open_scene(cfg, header, header_bytes, s);
+  int rc = open_scene(cfg, header, header_bytes, 0, s);
   if (rc != RT_OK) return rc;
   if (cfg->width <= 0 || cfg->height <= 0 || n > RT_QUERY_MAX_RAYS) return RT_E_INVAL;
   if (n == 0) return RT_OK;
@@ -159,8 +188,13 @@ int rt_pixel_rays_host(const rt_config* cfg, const void* header, size_t header_b
 
 int rt_occluded_host(const rt_config* cfg, const void* header, size_t header_bytes, const float* from,
                      const float* to, size_t n, uint8_t* out) {
+  return rt_occluded_host_ex(cfg, header, header_bytes, from, to, n, 0, out);
+}
+
+int rt_occluded_host_ex(const rt_config* cfg, const void* header, size_t header_bytes, const float* from,
+                        const float* to, size_t n, int flags, uint8_t* out) {
   Scene s;
-  int rc = open_scene(cfg, header, header_bytes, s);
+  int rc = open_scene(cfg, header, header_bytes, flags, s);
   if (rc != RT_OK) return rc;
   if (n > RT_QUERY_MAX_RAYS) return RT_E_INVAL;
   if (n == 0) return RT_OK;

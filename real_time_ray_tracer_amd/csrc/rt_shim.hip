@@ -109,6 +109,8 @@ struct rt_ctx {
   float4* d_batch = nullptr;   // rt_compute_frames: device table copies, 2 x kBatch slots (one per distinct table)
   int batch_last = -1;         // the d_batch slot d_shapes points into after rt_compute_frames (else -1)
   bool phong_gbuf = false;       // rt_set_phong_gbuffer: modes 3/4 write normals and depth, over the band
+  bool rectangles = false;       // rt_set_rectangles: shape id 3 is intersected (include/rt/abi.h "Rectangles")
+  int nrects = 0;                // rectangles in effect in the table the next dispatch reads (among nplanes)
   float4* d_mf_rb = nullptr;   // rt_compute_frames, mode 2: the rand_buffers of a multi-frame launch
   std::vector<float4> batch_host;
   std::vector<float> batch_hdr;  // the batch's host headers (camera, light: launch parameters)
@@ -131,6 +133,11 @@ int hip_fail(rt_ctx* c, hipError_t e) {
 
 size_t slot_elems(const rt_ctx* c) { return (size_t)c->band_rows * c->cfg.width; }
 int table_stride(const rt_ctx* c) { return rt::table_stride(c->cfg); }
+int scene_flags(const rt_ctx* c) { return c->rectangles ? RT_SCENE_RECTANGLES : 0; }
+// rows of the context's table that an upload carries: the rectangle region only when some are in effect
+size_t table_rows(const rt_ctx* c, int nrects) {
+  return nrects > 0 ? c->table.size() : rt::table_vec4(table_stride(c), c->cfg.spp);
+}
 rt::Row* rows(float4* tab) { return reinterpret_cast<rt::Row*>(tab); }
 
 int staged_copy(rt_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
@@ -232,6 +239,7 @@ void fill_params(const rt_ctx* c, int frame, rt::FrameParams& p) {
   p.S = table_stride(c);
   p.nplanes = c->nplanes;
   p.ncl = c->ncl;
+  p.nrects = c->nrects;
   p.spp = c->cfg.spp;
   p.inv_spp = 1.0f / (float)c->cfg.spp;
   p.fW = (float)c->cfg.width;
@@ -502,7 +510,7 @@ int rt_create(int device, const rt_config* cfg, rt_ctx** out) {
   if (e == hipSuccess) e = hipMemsetAsync(x->d_image_own, 0, (size_t)x->own_rows * c.width * sizeof(float4), x->stream);
   const int Sc = table_stride(x);
   for (int k = 0; k < kAoStreams; ++k) {
-    if (e == hipSuccess) e = hipMalloc(&x->d_shapes_buf[k], rt::table_vec4(Sc, c.spp) * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc(&x->d_shapes_buf[k], rt::table_vec4_rect(Sc, c.spp) * sizeof(float4));
     if (e == hipSuccess) x->d_rb_buf[k] = x->d_shapes_buf[k] + rt::rand_table(Sc);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
@@ -517,7 +525,7 @@ int rt_create(int device, const rt_config* cfg, rt_ctx** out) {
   x->d_rb = x->d_rb_buf[0];
   x->out_stream = x->own_stream;
   x->header.assign(rt_header_bytes(c.num_shapes, c.spp) / 4, 0.0f);
-  x->table.assign(rt::table_vec4(Sc, c.spp), make_float4(0, 0, 0, 0));
+  x->table.assign(rt::table_vec4_rect(Sc, c.spp), make_float4(0, 0, 0, 0));  // (the rectangle rows: rt_set_rectangles)
   *out = x;
   return RT_OK;
 }
@@ -628,10 +636,10 @@ int rt_upload_header(rt_ctx* c, const void* header, size_t bytes) {
   const int S = c->cfg.num_shapes, spp = c->cfg.spp;
   if (bytes != rt_header_bytes(S, spp)) return RT_E_INVAL;
   const float* h = (const float*)header;
-  int nobj = 0, np = 0, ncl = 0;
+  int nobj = 0, np = 0, ncl = 0, nr = 0;
   if (rt::header_nobj(h, S) < 0) return RT_E_INVAL;  // (before the context's header changes)
-  std::memcpy(c->header.data(), header, bytes);
-  int rc = rt::pack_header(c->cfg, h, rows(c->table.data()), nobj, np, ncl);
+  if (h != c->header.data()) std::memcpy(c->header.data(), header, bytes);
+  int rc = rt::pack_header(c->cfg, h, rows(c->table.data()), nobj, np, ncl, scene_flags(c), nr);
   if (rc != RT_OK) return rc;
   RT_HIP(c, hipSetDevice(c->device));
   // pipelined: into the header copy of the next frame, on its AO stream (ordered after the AO
@@ -642,13 +650,15 @@ int rt_upload_header(rt_ctx* c, const void* header, size_t bytes) {
     if (sr != RT_OK) return sr;
   }
   // table + rand_buffer in one upload (per-frame host cost matters for small strips/frames)
-  rc = staged_copy(c, c->d_shapes_buf[hc], c->table.data(), c->table.size() * sizeof(float4), ao_stream(c));
+  // (the rectangle rows behind rand_buffer travel only when a rectangle is in effect)
+  rc = staged_copy(c, c->d_shapes_buf[hc], c->table.data(), table_rows(c, nr) * sizeof(float4), ao_stream(c));
   if (rc != RT_OK) return rc;
   c->d_shapes = c->d_shapes_buf[hc];
   c->d_scene = c->d_shapes;
   c->d_rb = c->d_rb_buf[hc];
   c->nobj = nobj;
   c->nplanes = np;
+  c->nrects = nr;
   c->ncl = ncl;
   c->have_header = true;
   return RT_OK;
@@ -663,9 +673,15 @@ int rt_upload_rand_buffer(rt_ctx* c, const float* rb, size_t n_vec4) {
   int rc = staged_copy(c, c->d_rb_buf[hc], rb, n_vec4 * 16, ao_stream(c));
   if (rc != RT_OK) return rc;
   // the other copy keeps the shape table: bring it along when switching copies
-  if (c->d_shapes != c->d_shapes_buf[hc])
+  if (c->d_shapes != c->d_shapes_buf[hc]) {
     RT_HIP(c, hipMemcpyAsync(c->d_shapes_buf[hc], c->d_shapes, rt::rand_table(table_stride(c)) * sizeof(float4),
                              hipMemcpyDeviceToDevice, ao_stream(c)));
+    if (c->nrects > 0) {  // and the rectangle rows behind rand_buffer
+      const size_t r0 = rt::rect_table(table_stride(c), c->cfg.spp);
+      RT_HIP(c, hipMemcpyAsync(c->d_shapes_buf[hc] + r0, c->d_shapes + r0, (c->table.size() - r0) * sizeof(float4),
+                               hipMemcpyDeviceToDevice, ao_stream(c)));
+    }
+  }
   c->d_shapes = c->d_shapes_buf[hc];
   c->d_scene = c->d_shapes;
   c->d_rb = c->d_rb_buf[hc];
@@ -787,7 +803,7 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
   const size_t tb = tv * sizeof(float4);
   for (int k0 = 0; k0 < n; k0 += kBatch) {
     const int m = std::min(kBatch, n - k0);
-    std::vector<int> nobj(m), npl(m), ncl(m), slot(m), dslot(m);
+    std::vector<int> nobj(m), npl(m), ncl(m), nrc(m), slot(m), dslot(m);
     std::vector<unsigned char> same(m);  // frame j's table equals the previous frame's
     // the context's current table, if it already sits in a d_batch slot (host copy: c->table)
     const int prev = (c->batch_last >= 0 && c->d_shapes == c->d_batch + (size_t)c->batch_last * tv) ? c->batch_last : -1;
@@ -797,7 +813,7 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
     for (int j = 0; j < m; ++j) {
       float4* tab = c->batch_host.data() + (size_t)nd * tv;
       int rc = update(k0 + j, f);
-      if (rc == RT_OK) rc = rt::pack_header(c->cfg, header, rows(tab), nobj[j], npl[j], ncl[j]);
+      if (rc == RT_OK) rc = rt::pack_header(c->cfg, header, rows(tab), nobj[j], npl[j], ncl[j], scene_flags(c), nrc[j]);
       if (rc != RT_OK) return rc;
       std::memcpy(c->batch_hdr.data() + (size_t)j * hf, header, bytes);  // camera / light of frame j
       slot[j] = f;
@@ -822,6 +838,7 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
       c->d_rb = c->d_shapes + rt::rand_table(Sc);
       c->nobj = nobj[j];
       c->nplanes = npl[j];
+      c->nrects = nrc[j];
       c->ncl = ncl[j];
       c->have_header = true;
       std::memcpy(c->header.data(), c->batch_hdr.data() + (size_t)j * hf, bytes);  // launch parameters
@@ -859,6 +876,27 @@ int rt_set_phong_gbuffer(rt_ctx* c, int on) {
 }
 
 int rt_phong_gbuffer(rt_ctx* c) { return c ? (c->phong_gbuf ? 1 : 0) : RT_E_INVAL; }
+
+int rt_set_rectangles(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  if (c->rectangles == (on != 0)) return RT_OK;
+  RT_HIP(c, hipSetDevice(c->device));
+  int rc = drain(c);  // no launch in flight reads the tables replaced or freed here
+  if (rc != RT_OK) return rc;
+  streams_idle(c);
+  c->rectangles = on != 0;
+  // what depended on the old table starts over: the cull cache's key and masks, the tile schedule's
+  // costs and order, and the packed table itself (the header last given, packed and uploaded again)
+  c->sched.release();
+  c->cull.have_key = false;
+  rc = c->cull.invalidate(c->last_hip);
+  if (rc != RT_OK) return rc;
+  c->batch_last = -1;
+  if (c->have_header) rc = rt_upload_header(c, c->header.data(), c->header.size() * sizeof(float));
+  return rc;
+}
+
+int rt_rectangles(rt_ctx* c) { return c ? (c->rectangles ? 1 : 0) : RT_E_INVAL; }
 
 int rt_tile_schedule_state(rt_ctx* c) {
   if (!c) return RT_E_INVAL;
@@ -1147,6 +1185,7 @@ static rt::QueryScene query_scene(const rt_ctx* c) {
   s.S = table_stride(c);
   s.nobj = c->nobj;
   s.nplanes = c->nplanes;
+  s.nrects = c->nrects;
   s.fW = (float)c->cfg.width;
   s.fH = (float)c->cfg.height;
   const float *h = hv(c, RT_HDR_HORIZONTAL), *v = hv(c, RT_HDR_VERTICAL), *l = hv(c, RT_HDR_LLC_MINUS_CAMPOS),

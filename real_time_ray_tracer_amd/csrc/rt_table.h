@@ -44,5 +44,12 @@ RT_HD constexpr size_t camrel_table(int S) {
 }
 RT_HD constexpr size_t rand_table(int S) { return camrel_table(S) + (size_t)S; }
 RT_HD constexpr size_t table_vec4(int S, int spp) { return rand_table(S) + (size_t)2 * spp; }
+// Rectangles in effect (rt_set_rectangles, include/rt/abi.h "Rectangles") enter the plane table in
+// ascending index order with the planes, as (n, bits(index)), (llc, bits(offset)): offset != 0 is the
+// distance in float4 from the plane table's base to the rectangle's two rows in a region appended to
+// the table, [2 S) rows behind rand_buffer: (right, dot(right, right)), (up, dot(up, up)).  A plane's
+// second row keeps w = 0.  Nothing above moves; a table packed without rectangles ends at table_vec4.
+RT_HD constexpr size_t rect_table(int S, int spp) { return table_vec4(S, spp); }
+RT_HD constexpr size_t table_vec4_rect(int S, int spp) { return rect_table(S, spp) + (size_t)2 * S; }
 
 }  // namespace rt

@@ -312,6 +312,17 @@ class Renderer:
         default, as in the reference).  The colours do not depend on it."""
         self._c(self._lib.rt_set_phong_gbuffer(self.ctx, int(bool(on))), "rt_set_phong_gbuffer")
 
+    def set_rectangles(self, on: bool):
+        """Intersect rectangles (shape id 3) in every mode and in the ray queries, by the rule of
+        include/rt/abi.h "Rectangles" (rt_set_rectangles; off by default, as the reference never hits
+        them).  Takes effect at the next launch or query."""
+        self._c(self._lib.rt_set_rectangles(self.ctx, int(bool(on))), "rt_set_rectangles")
+
+    @property
+    def rectangles(self) -> bool:
+        """Whether rectangles are intersected (rt_rectangles)."""
+        return bool(self._c(self._lib.rt_rectangles(self.ctx), "rt_rectangles"))
+
     @property
     def phong_gbuffer(self) -> bool:
         """Whether modes 3 and 4 write normals and depth (rt_phong_gbuffer)."""
@@ -648,6 +659,11 @@ class StripGroup:
         strips are re-created by set_bounds, set_plan or balance."""
         self._c(self._lib.rt_group_set_phong_gbuffer(self.g, int(bool(on))), "rt_group_set_phong_gbuffer")
 
+    def set_rectangles(self, on: bool):
+        """Renderer.set_rectangles on every strip (rt_group_set_rectangles); kept when the strips are
+        re-created."""
+        self._c(self._lib.rt_group_set_rectangles(self.g, int(bool(on))), "rt_group_set_rectangles")
+
     def bind_frame(self, device_ptr: int | None):
         self._c(self._lib.rt_group_bind_frame(self.g, C.c_void_p(device_ptr) if device_ptr else None),
                 "rt_group_bind_frame")
@@ -740,15 +756,24 @@ def _query_cfg(header: Header, width: int = 1, height: int = 1):
     return _lib.rt_config(int(width), int(height), header.S, header.AA, 1, 1, 0, 0)
 
 
-def trace_rays_host(header: Header, origins, dirs, thr: float = 1e-4) -> Hits:
-    """rt_trace_rays_host (host only): Renderer.trace_rays' rule in C on `header`, its specification."""
+def rectangle_eval_host(shape, pos, dir) -> float:
+    """rt_rectangle_eval_host (host only): the rectangle rule (include/rt/abi.h "Rectangles") for one
+    packed shape row (20 floats) and one ray; t, or -1 for a miss."""
+    s = np.ascontiguousarray(shape, np.float32).reshape(20)
+    return float(_lib.load().rt_rectangle_eval_host(fptr(s), _f3(pos), _f3(dir)))
+
+
+def trace_rays_host(header: Header, origins, dirs, thr: float = 1e-4, rectangles: bool = False) -> Hits:
+    """rt_trace_rays_host_ex (host only): Renderer.trace_rays' rule in C on `header`, its specification;
+    rectangles: as with Renderer.set_rectangles on (RT_SCENE_RECTANGLES)."""
     o, d = _rows(origins, 3, np.float32), _rows(dirs, 3, np.float32)
     if len(o) != len(d):
         raise ValueError(f"trace_rays_host: {len(o)} origins, {len(d)} directions")
     h = Hits.empty(len(o))
-    _check(_lib.load().rt_trace_rays_host(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
-                                          header.data.nbytes, fptr(o), fptr(d), len(o), thr, fptr(h.t), _iptr(h.ind),
-                                          fptr(h.normals)), "rt_trace_rays_host")
+    _check(_lib.load().rt_trace_rays_host_ex(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
+                                             header.data.nbytes, fptr(o), fptr(d), len(o), thr,
+                                             _lib.RT_SCENE_RECTANGLES if rectangles else 0, fptr(h.t), _iptr(h.ind),
+                                             fptr(h.normals)), "rt_trace_rays_host_ex")
     return h
 
 
@@ -763,15 +788,17 @@ def pixel_rays_host(header: Header, width: int, height: int, xy):
     return o, d
 
 
-def occluded_host(header: Header, a, b) -> np.ndarray:
-    """rt_occluded_host (host only): Renderer.occluded's rule in C on `header`, its specification."""
+def occluded_host(header: Header, a, b, rectangles: bool = False) -> np.ndarray:
+    """rt_occluded_host_ex (host only): Renderer.occluded's rule in C on `header`, its specification;
+    rectangles: as with Renderer.set_rectangles on."""
     a, b = _rows(a, 3, np.float32), _rows(b, 3, np.float32)
     if len(a) != len(b):
         raise ValueError(f"occluded_host: {len(a)} start points, {len(b)} end points")
     out = np.zeros(len(a), np.uint8)
-    _check(_lib.load().rt_occluded_host(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
-                                        header.data.nbytes, fptr(a), fptr(b), len(a), out.ctypes.data_as(C.c_void_p)),
-           "rt_occluded_host")
+    _check(_lib.load().rt_occluded_host_ex(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
+                                           header.data.nbytes, fptr(a), fptr(b), len(a),
+                                           _lib.RT_SCENE_RECTANGLES if rectangles else 0,
+                                           out.ctypes.data_as(C.c_void_p)), "rt_occluded_host_ex")
     return out.astype(bool)
 
 
