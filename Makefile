@@ -40,13 +40,13 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
 
 # the host-only units (no HIP header): rt_host.cpp, rt_plan.cpp, rt_query_host.cpp
 $(OBJDIR)/rt_host.o $(OBJDIR)/rt_plan.o $(OBJDIR)/rt_query_host.o: $(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/*.h include/rt/*.h | $(OBJDIR)
-	$(HIPCC) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -c $< -o $@
+	$(HIPCC) -O3 -std=c++17 -fPIC -ffp-contract=off $(HIPFLAGS_EXTRA) -Wall -Iinclude -c $< -o $@
 
 $(OBJDIR)/rt_group.o: $(CSRC)/rt_group.cpp $(CSRC)/rt_kernels.h include/rt/*.h | $(OBJDIR)
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Iinclude -c $< -o $@
 
-# the shim and its components (rt_stage, rt_sched, rt_cull, rt_gbuf, rt_timing, rt_query), the host-only units, the group
-SHIM_OBJS := $(addprefix $(OBJDIR)/,rt_shim.o rt_stage.o rt_sched.o rt_cull.o rt_gbuf.o rt_timing.o rt_query.o rt_host.o \
+# the shim and its components (rt_stage, rt_sched, rt_cull, rt_gbuf, rt_timing, rt_query, rt_tree), the host-only units, the group
+SHIM_OBJS := $(addprefix $(OBJDIR)/,rt_shim.o rt_stage.o rt_sched.o rt_cull.o rt_gbuf.o rt_timing.o rt_query.o rt_tree.o rt_host.o \
                rt_plan.o rt_query_host.o rt_group.o)
 
 # BUILD_INFO: sha1 of the library's sources (+ the git commit they were built at, "+dirty" if

@@ -336,6 +336,71 @@ int rt_trace_rays_host_ex(const rt_config* cfg, const void* header, size_t heade
 int rt_occluded_host_ex(const rt_config* cfg, const void* header, size_t header_bytes, const float* from,
                         const float* to, size_t n, int flags, uint8_t* out);
 
+/* ---- Query tree ----------------------------------------------------------------------- */
+/* The three ray queries test every sphere for every ray.  rt_set_query_tree(ctx, 1) makes them walk
+ * a tree of bounding balls over the scene's spheres instead; rt_set_query_tree(ctx, 0) restores the
+ * linear scan; rt_query_tree reads the switch (1 / 0).  Off by default, and a context that never
+ * switches it on allocates nothing, builds nothing and launches what it launched before.  The
+ * answers are those of the linear scan, bit for bit: t, ind, normals, dirs and the occlusion bytes,
+ * for every ray, NaN and infinite operands and directions of any length included.  The frame
+ * programs do not use the tree.
+ *   Members.  The tree is over the packed sphere rows (centre, r) of indices [0, nobj).  Rows of
+ *   other shapes are left out, and so is a sphere whose radius is NaN (sphere_eval_ray gives NaN for
+ *   it on every ray, so nothing ever takes it; the table packs it as such a row).  A sphere whose
+ *   geometry is otherwise not finite, or whose |r| exceeds 8 times
+ *   the median |r| of the finite spheres (a ground sphere), is no member: it goes to the "always"
+ *   list, which every ray tests.  With fewer than 8 members (twice the leaf size, 4) no tree is
+ *   built and the queries run the linear scan.
+ *   Shape.  Recursive median splits of the members' centres along the widest axis, ties by index,
+ *   down to leaves of 1 to 4 spheres; deterministic.  The nodes are stored in preorder, each with a
+ *   ball (centre, R) and a skip link, the index of the next node that is not below it; a leaf also
+ *   names a range of the leaf table (the sphere rows in leaf order, each with its index).  A
+ *   traversal needs no stack: at node k it goes to k + 1 when the ray may hit the ball (after
+ *   testing the members if k is a leaf), else to skip[k], and ends at the node count.
+ *   Invariant.  For a leaf |c_i - centre| + |r_i| <= R for every member, for an inner node
+ *   |centre_child - centre| + R_child <= R for both children (computed in binary64, rounded up), so
+ *   every sphere below a node lies inside the node's ball.
+ *   Node test.  The conservative ray-versus-ball test of the AO kernel's bounce clusters
+ *   (RT_MATH_CULL_CLUSTER): it rejects a ball only when every sphere inside it has a negative
+ *   computed discriminant or both roots negative, which no threshold >= 0 accepts and no shadow ray
+ *   counts; NaN keeps the ball.  Its proof needs a unit direction, so a ray is culled only behind
+ *   the unit gate: s = dot(d, d) as the fused chain fma(z, z, fma(y, y, x*x)) with
+ *   |s - 1| <= 4.2e-7f.  Every normalize() result passes (pixel rays, rt_occluded's l).  A direction
+ *   that fails the gate, NaN included, keeps every ball and so visits every sphere.
+ *   Members, planes and rectangles are tested by the rules above ("ray queries", "Rectangles") and
+ *   merged by (t, index): the candidate of least t and, among equal t, least index, which is what
+ *   the ascending scan ends with.  Nothing is pruned by the closest t found so far.
+ * Switching on allocates one device buffer, sized for num_shapes spheres (84 bytes per shape); no
+ * later call allocates device memory for the tree (RT_E_NOMEM when it cannot be had; the switch
+ * stays off).  If a header is in effect the tree is built at once.  While on, every call that gives
+ * the context a header (rt_upload_header, rt_compute_frames, the host-buffer calls,
+ * rt_set_rectangles) rebuilds the tree on the host and uploads it through the staging ring on
+ * rt_get_stream(ctx), but only when nobj or one of the first nobj sphere rows differs, byte for
+ * byte, from the last build's: a loop that moves the light or replaces rand_buffer builds once.
+ * The _device queries keep their contract (no allocation, no host wait, no event or stream
+ * created).  Switching off waits for the context's streams, then frees the buffer. */
+int rt_set_query_tree(rt_ctx* ctx, int on);
+int rt_query_tree(rt_ctx* ctx); /* 1 = on, 0 = off; RT_E_INVAL for NULL */
+/* Diagnostic, like rt_cull_cache_stats: nodes, leaves and always-list entries of the tree of the
+ * scene in effect (all 0 when the switch is off or the scene has no tree) and the bytes of the
+ * device buffer (0 when off; unchanged by any call while on).  Any pointer may be NULL. */
+int rt_query_tree_stats(rt_ctx* ctx, int* nodes, int* leaves, int* always, size_t* bytes);
+/* Host only: the tree that an upload of `header` (rt_header_bytes(num_shapes, spp) bytes) builds
+ * for a context created with `cfg`; never touches the GPU.  flags: 0 or RT_SCENE_RECTANGLES, as for
+ * rt_trace_rays_host_ex; it does not change which rows are spheres, so the tree is the same, and any
+ * other bit is refused.  Written for n nodes, e leaf entries and a always entries:
+ *   balls[4k .. 4k+3] = node k's (centre, R);  links[4k .. 4k+3] = (skip, first, count, 0), count 0
+ *   for an inner node, else the leaf's entries [first, first + count) of the leaf table;
+ *   leaf_rows[4j .. 4j+3] = entry j's sphere row, leaf_index[j] its index;  always[0 .. a) the
+ *   always list's indices, ascending.
+ * Returns n, 0 when no tree is built (then e = a = 0: the linear scan tests every sphere), -1 for an
+ * invalid configuration, header or flags, a NULL array, or when n > node_cap, e > leaf_cap or
+ * a > always_cap.  num_shapes entries suffice for leaf_cap and always_cap, 2 * num_shapes for
+ * node_cap.  n_leaf / n_always (either may be NULL) receive e and a. */
+int rt_query_tree_host(const rt_config* cfg, const void* header, size_t header_bytes, int flags, float* balls,
+                       int32_t* links, int node_cap, float* leaf_rows, int32_t* leaf_index, int leaf_cap,
+                       int32_t* always, int always_cap, int* n_leaf, int* n_always);
+
 /* ---- 8-bit display output (the blit, src/main.cpp:783-797) -------------------------- */
 /* The reference ends a frame by drawing the rgba32f image into an 8-bit framebuffer
  * (src/main.cpp:783-797 through resources/shader_fragment.glsl:9-19: colour unchanged, alpha 1).
@@ -461,6 +526,8 @@ int rt_group_enable_pipelining(rt_group* g, int on);
 int rt_group_set_phong_gbuffer(rt_group* g, int on);
 /* rt_set_rectangles on every strip; kept in the same way. */
 int rt_group_set_rectangles(rt_group* g, int on);
+/* rt_set_query_tree on every strip; kept in the same way. */
+int rt_group_set_query_tree(rt_group* g, int on);
 /* Assemble frames into a caller-owned device buffer of H*W float4 on devices[0] (NULL: the
  * group's own).  Waits for the frames in flight first. */
 int rt_group_bind_frame(rt_group* g, void* device_ptr);
@@ -621,10 +688,16 @@ enum {
                              cluster (centre, R) 4, member sphere 4 = 14 floats.  out 3: may = the
                              ray may hit the cluster; the lane's bit of the wave-mask form of the
                              same test; the member's t accepted at 0.0001                          */
-  RT_MATH_CULL_SHADOW = 16  /* one wavefront per case.  in: light 3, sphere 4, then per lane shaded
+  RT_MATH_CULL_SHADOW = 16, /* one wavefront per case.  in: light 3, sphere 4, then per lane shaded
                              point 3, need (non-zero) = 263 floats; at least one lane in need.  out,
                              2 per lane = 128: keep = the cone at the light over the needing lanes
                              does not exclude the sphere; occ = the lane's shadow ray is occluded   */
+  RT_MATH_CULL_TREE = 17    /* the query tree's kernels ("Query tree").  RT_MATH_CULL_CLUSTER's cases
+                             under its rule: one lane per case, n a multiple of 64, in: origin 3,
+                             direction 3, ball (centre, R) 4, member sphere 4 = 14 floats.  out 3:
+                             gate = the direction passes the unit gate; may = the tree kernels' node
+                             decision, !gate || the cluster test; the member's t as their member test
+                             accepts it from t = -1 at threshold 0 (-1: not accepted)              */
 };
 int rt_selftest_math(rt_ctx* ctx, int fn, const float* in, float* out, size_t n);
 

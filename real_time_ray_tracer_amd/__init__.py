@@ -5,10 +5,11 @@ from ._lib import RtError, load  # noqa: F401
 from .host import (AO_COMPUTE, AOP_COMPUTE, AOP_POSTPROCESSING, ASPECT_RATIO,  # noqa: F401
                    FULLSCREEN_ASPECT_RATIO, H_COMPUTE, P_COMPUTE, FrameDriver, GBuffer, Header, Hits,
                    Renderer, SSBO, StripGroup, aspect_for, header_floats, occluded_host, pixel_rays_host,
-                   quantize_rgba8, resample_rgba8, ssbo_floats, trace_rays_host, rectangle_eval_host)
+                   quantize_rgba8, query_tree_host, resample_rgba8, ssbo_floats, trace_rays_host,
+                   rectangle_eval_host)
 
 __all__ = ["RtError", "load", "Renderer", "StripGroup", "Header", "SSBO", "GBuffer", "FrameDriver",
            "AOP_COMPUTE", "AOP_POSTPROCESSING", "AO_COMPUTE", "P_COMPUTE", "H_COMPUTE",
            "ASPECT_RATIO", "FULLSCREEN_ASPECT_RATIO", "aspect_for", "header_floats", "ssbo_floats",
            "quantize_rgba8", "resample_rgba8", "Hits", "trace_rays_host", "pixel_rays_host", "occluded_host",
-           "rectangle_eval_host"]
+           "rectangle_eval_host", "query_tree_host"]

@@ -23,7 +23,7 @@ RT_MODE_AO_PP, RT_MODE_AO, RT_MODE_PHONG, RT_MODE_PHONG_REFL = 1, 2, 3, 4
 (RT_MATH_SIN, RT_MATH_RANDOM, RT_MATH_SQRT, RT_MATH_DIV, RT_MATH_NORMALIZE, RT_MATH_SPHERE, RT_MATH_SQRT_SWEEP,
  RT_MATH_RCP_SWEEP, RT_MATH_SQRT_TAIL_SWEEP, RT_MATH_SIN_RANGE, RT_MATH_SHADOW,
  RT_MATH_SIN_TABLE, RT_MATH_CULL_CAMERA, RT_MATH_CULL_PLANE, RT_MATH_CULL_BOUNCE, RT_MATH_CULL_CLUSTER,
- RT_MATH_CULL_SHADOW) = range(17)
+ RT_MATH_CULL_SHADOW, RT_MATH_CULL_TREE) = range(18)
 RT_NUM_FRAMES = 8
 RT_RECURSION_DEPTH = 20
 RT_SHAPE_SPHERE, RT_SHAPE_RECTANGLE, RT_SHAPE_PLANE = 1, 3, 5
@@ -66,6 +66,12 @@ SIGNATURES = {
     "rt_phong_gbuffer": (C.c_int, [_ctx]),
     "rt_set_rectangles": (C.c_int, [_ctx, C.c_int]),
     "rt_rectangles": (C.c_int, [_ctx]),
+    "rt_set_query_tree": (C.c_int, [_ctx, C.c_int]),
+    "rt_query_tree": (C.c_int, [_ctx]),
+    "rt_query_tree_stats": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_size_t)]),
+    "rt_query_tree_host": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, C.c_int, _fp, _ip, C.c_int, _fp, _ip, C.c_int,
+                                     _ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_tile_schedule_state": (C.c_int, [_ctx]),
     "rt_tile_schedule_orders": (C.c_int, [_ctx]),
     "rt_set_cull_cache": (C.c_int, [_ctx, C.c_int]),
@@ -124,6 +130,7 @@ SIGNATURES = {
     "rt_group_enable_pipelining": (C.c_int, [_grp, C.c_int]),
     "rt_group_set_phong_gbuffer": (C.c_int, [_grp, C.c_int]),
     "rt_group_set_rectangles": (C.c_int, [_grp, C.c_int]),
+    "rt_group_set_query_tree": (C.c_int, [_grp, C.c_int]),
     "rt_group_bind_frame": (C.c_int, [_grp, _vp]),
     "rt_group_frame_device_ptr": (_vp, [_grp]),
     "rt_group_upload_header": (C.c_int, [_grp, _vp, C.c_size_t]),

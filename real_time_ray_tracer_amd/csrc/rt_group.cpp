@@ -116,6 +116,7 @@ struct rt_group {
   bool pipelined = false;
   bool phong_gbuf = false;  // rt_group_set_phong_gbuffer: kept across re-created strips, as pipelining is
   bool rectangles = false;  // rt_group_set_rectangles: kept in the same way
+  bool query_tree = false;  // rt_group_set_query_tree: kept in the same way
   std::vector<rt_ctx*> ctx;
   float4* frame_own = nullptr;  // [H][W] on devices[0]
   float4* frame = nullptr;      // the bound frame (own or the caller's)
@@ -190,6 +191,7 @@ int make_strips(rt_group* g) {
     if (rc == RT_OK && g->pipelined) rc = rt_enable_pipelining(g->ctx[i], 1, nullptr);
     if (rc == RT_OK && g->phong_gbuf) rc = rt_set_phong_gbuffer(g->ctx[i], 1);
     if (rc == RT_OK && g->rectangles) rc = rt_set_rectangles(g->ctx[i], 1);
+    if (rc == RT_OK && g->query_tree) rc = rt_set_query_tree(g->ctx[i], 1);
     if (rc != RT_OK) {
       destroy_strips(g);
       return rc;
@@ -628,6 +630,16 @@ int rt_group_set_rectangles(rt_group* g, int on) {
   g->rectangles = on != 0;
   for (auto* c : g->ctx) {
     int rc = rt_set_rectangles(c, on);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+int rt_group_set_query_tree(rt_group* g, int on) {
+  if (!g) return RT_E_INVAL;
+  g->query_tree = on != 0;
+  for (auto* c : g->ctx) {
+    int rc = rt_set_query_tree(c, on);
     if (rc != RT_OK) return rc;
   }
   return RT_OK;

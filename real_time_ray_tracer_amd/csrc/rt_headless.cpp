@@ -10,7 +10,7 @@
 //
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
 //               [--scene synthetic|1|5|6|7] [--rectangles 0|1] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
-//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH] [--pick X,Y]
+//               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH] [--pick X,Y] [--query-tree 0|1]
 // --pick X,Y prints, after the last frame, one line `pick x y ind t nx ny nz`: the closest hit of pixel
 // (X, Y)'s primary ray (frame coordinates, row 0 = the bottom row) by rt_trace_pixels at threshold 0.
 // --rectangles 1 turns rt_set_rectangles on (rt_group_set_rectangles with --strips): rectangles are drawn,
@@ -117,7 +117,7 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
 }
 
 int main(int argc, char** argv) {
-  int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0, rectangles = 0;
+  int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0, rectangles = 0, query_tree = 0;
   int ppm_w = 0, ppm_h = 0;  // --ppm-size (0: the frame's own size)
   bool pick = false;         // --pick X,Y: what is under that pixel after the last frame
   int pick_x = 0, pick_y = 0;
@@ -137,6 +137,7 @@ int main(int argc, char** argv) {
     else if (k == "--ppm") ppm = v;
     else if (k == "--pipeline") pipeline = std::atoi(v.c_str());
     else if (k == "--rectangles") rectangles = std::atoi(v.c_str());
+    else if (k == "--query-tree") query_tree = std::atoi(v.c_str());  // --pick through the query tree (rt_set_query_tree)
     else if (k == "--strips") strips = std::atoi(v.c_str());
     else if (k == "--devices") devlist = v;
     else if (k == "--balance") balance = std::atoi(v.c_str());
@@ -174,6 +175,7 @@ int main(int argc, char** argv) {
   check(rt_enable_timing(ctx, 1), "rt_enable_timing");
   if (pipeline) check(rt_enable_pipelining(ctx, 1, nullptr), "rt_enable_pipelining");
   if (rectangles) check(rt_set_rectangles(ctx, 1), "rt_set_rectangles");
+  if (query_tree) check(rt_set_query_tree(ctx, 1), "rt_set_query_tree");
   int frame = 0;
   auto t0 = std::chrono::steady_clock::now();
   for (int k = 0; k < frames; ++k) {

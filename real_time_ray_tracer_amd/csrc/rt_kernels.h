@@ -193,11 +193,23 @@ struct RayQuery {
   float* nrm;
   float* dir_out;
 };
-hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream);
+// The query tree of the scene's spheres (include/rt/abi.h "Query tree"; rt_plan build_query_tree),
+// passed beside the scene: QueryScene and RayQuery stay as they are, and so do the kernels that take
+// them.  nodes: two float4 per node in preorder, the ball (centre, R) and the bits of (skip, first,
+// count, 0); rows / index: the leaf table, then the n_always entries of the always list from
+// always_first on.  n_nodes == 0 or a null pointer: no tree, the linear kernels.
+struct QueryTree {
+  const float4* nodes;
+  const float4* rows;
+  const int* index;
+  int n_nodes, always_first, n_always;
+};
+// tree non-null with n_nodes > 0: ray_query_tree_kernel / occluded_tree_kernel, the same answers bit for bit
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree = nullptr);
 // Occlusion of n segments from[i] -> to[i] ([n][3] each): out[i] = 1 when shadow_ray(pos = from[i],
 // light = to[i]) finds an occluder (p_compute.glsl:145-166), else 0.  Same instantiations and limits.
 hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
-                           hipStream_t stream);
+                           hipStream_t stream, const QueryTree* tree = nullptr);
 
 // Device math self-test (rt_selftest_math).
 hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream);

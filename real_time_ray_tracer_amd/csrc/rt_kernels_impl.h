@@ -450,6 +450,42 @@ __device__ __forceinline__ unsigned long long cluster_may_hit_mask(f3 p, f3 d, f
   return nlm & (nc1 | nc2);
 }
 
+// ---- the query tree's device functions (the kernels: "The query tree" below; here, ahead of the
+// self-test kernel, which runs them alone as RT_MATH_CULL_TREE) ----
+// The unit gate.  cluster_may_hit's proof takes a direction with | |d| - 1 | <= 3e-7, and
+// rt_trace_rays takes d as given, so a lane culls only when s = dot(d, d), the fused chain, has
+// |s - 1| <= kUnitGate.  s - 1 is exact (Sterbenz) and a multiple of 2^-24 below 1, of 2^-23 above,
+// so the gate admits s in [1 - 7 * 2^-24, 1 + 3 * 2^-23] = [1 - 4.1724e-7, 1 + 3.5763e-7].  The
+// chain rounds three times, each partial sum at most the total: |s - E| <= 3 * 2^-24 E (1 + 2^-24)^2
+// < 1.7882e-7 for the exact E = |d|^2 <= 1 + 6e-7.  Hence E in [1 - 5.9606e-7, 1 + 5.3645e-7] and
+// |d| = sqrt(E) in [1 - 2.9804e-7, 1 + 2.6823e-7], inside the proof's 3e-7.  A direction that fails
+// (NaN included: the comparison is false) keeps every ball, so its lane visits every leaf and gets
+// the linear scan's answer.  normalize()'s outputs pass: over 4 * 10^7 random vectors s stayed in
+// [1 - 6 * 2^-24, 1 + 3 * 2^-23] (and tests/test_gpu_query_tree.py holds it on the device).
+constexpr float kUnitGate = 4.2e-7f;
+__device__ __forceinline__ bool unit_gate(f3 d) { return fabsf(dot(d, d) - 1.0f) <= kUnitGate; }
+// A node's decision: cluster_may_hit itself (NaN keeps the node), for a lane that passed the gate.
+__device__ __forceinline__ bool tree_may_hit(bool gate, f3 o, f3 d, float4 cb) { return !gate || cluster_may_hit(o, d, cb); }
+
+// One sphere of the tree's closest-hit walk: query_sphere's value arithmetic (the same dot, fmaf
+// discriminant, sqrt_rn, root selection and del == 0 case) per lane, without its wave-uniform ballot
+// branch (the sphere differs from lane to lane here), merged by planar_candidate's order-free rule:
+// the accepted candidate of least t and, among equal t, least index, which is what the ascending
+// scan with its strict '<' ends with.
+__device__ __forceinline__ void tree_sphere(f3 pos, f3 dir, float4 g, int i, float thr, float& t, int& ind) {
+  const f3 pmc = pos - xyz(g);
+  const float b = dot(dir, pmc);
+  const float del = fmaf(g.w, g.w, fmaf(b, b, -dot(pmc, pmc)));
+  const float s = sqrt_rn(del);
+  const float nb = -1.0f * b;
+  const float t1 = nb + s, t2 = nb - s;
+  float res = (t2 < 0.0f) ? ((t1 < 0.0f) ? -1.0f : t1) : t2;
+  res = (del == 0.0f) ? nb : res;
+  const bool acc = (del >= 0.0f) & (res > thr) & ((t < 0.0f) | (res < t) | ((res == t) & (i < ind)));
+  t = acc ? res : t;
+  ind = acc ? i : ind;
+}
+
 // ---------------------------------------------------------------------------------------
 // Planes (plane_eval_ray, p_compute.glsl:111-119) in the cone-culled kernels.  The spheres
 // keep their culled, ascending scan over the sphere table (P.sph: planes and every other
@@ -2541,6 +2577,19 @@ __global__ void selftest_kernel(int fn, const float* __restrict__ in, float* __r
       out[3 * i + 2] = t;
       break;
     }
+    case 17: {  // the query tree's unit gate, node decision and member test (thr 0, from t = -1)
+      const float* a = in + 14 * i;
+      const f3 p = mk(a[0], a[1], a[2]), d = mk(a[3], a[4], a[5]);
+      const float4 cb = make_float4(a[6], a[7], a[8], a[9]), g = make_float4(a[10], a[11], a[12], a[13]);
+      const bool gate = unit_gate(d);
+      float t = -1.0f;
+      int ind = -1;
+      tree_sphere(p, d, g, 0, 0.0f, t, ind);
+      out[3 * i] = gate ? 1.0f : 0.0f;
+      out[3 * i + 1] = tree_may_hit(gate, p, d, cb) ? 1.0f : 0.0f;
+      out[3 * i + 2] = t;
+      break;
+    }
     case 16: {  // shadow cone at the light over one wave's shaded points vs sphere
       const int lane = threadIdx.x & 63;
       const float* a = in + 263 * i;
@@ -3245,12 +3294,133 @@ __global__ __launch_bounds__(kBlock) void occluded_rc_kernel(QueryScene sc, cons
   out[i] = occ ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// The query tree (include/rt/abi.h "Query tree"; rt_plan build_query_tree): the queries above over
+// a tree of balls around the spheres, the same answers bit for bit.
+// ---------------------------------------------------------------------------------------
+// The closest hit of a ray over the tree: the always list (wave-uniform entries: scalar loads), the
+// tree, each lane walking the preorder array with its own index (vector loads: the lanes diverge),
+// then every entry of the plane table as query_closest_rc scans it (a plane's entry has offset 0, so
+// planar_candidate<true> is plane_candidate on it; plane_eval on the plane table's rows is plane_eval
+// on geo / geo2: the same normal and p0).  No stack: a node whose ball may be hit is followed by its
+// first child or, for a leaf, by its members and then the next node; any other by its skip link.
+// A culled ball's members are never accepted by the linear scan (cluster_may_hit's cases (A) and
+// (B): a computed del < 0, or both roots negative, which no thr >= 0 accepts), and the merge does not
+// depend on the order, so (t, ind) are the linear scan's.  Nothing is pruned by the current t.
+__device__ __forceinline__ int tree_closest(const QueryScene& sc, const QueryTree& T, f3 pos, f3 dir, float thr,
+                                            float& t_out) {
+  float t = -1.0f;
+  int ind = -1;
+  const float4* __restrict__ rows = T.rows;
+  const int* __restrict__ index = T.index;
+  for (int e = T.always_first; e < T.always_first + T.n_always; ++e) tree_sphere(pos, dir, rows[e], index[e], thr, t, ind);
+  const bool gate = unit_gate(dir);
+  const float4* __restrict__ nodes = T.nodes;
+  for (int k = 0; k < T.n_nodes;) {
+    const float4 cb = nodes[2 * k], lk = nodes[2 * k + 1];
+    if (tree_may_hit(gate, pos, dir, cb)) {
+      const int first = __float_as_int(lk.y), count = __float_as_int(lk.z);
+      for (int j = 0; j < count; ++j) tree_sphere(pos, dir, rows[first + j], index[first + j], thr, t, ind);
+      k = k + 1;
+    } else {
+      k = __float_as_int(lk.x);
+    }
+  }
+  const float4* __restrict__ planes = sc.shapes + plane_table(sc.S);
+  for (int k = 0; k < sc.nplanes; ++k)
+    planar_candidate<true>(planes, pos, dir, planes[2 * k], planes[2 * k + 1], thr, t, ind);
+  t_out = t;
+  return ind;
+}
+
+// ray_query_rc_kernel over the tree: the rays, normals and dir_out formed exactly as there
+// (shape_normal_rc<true> is shape_normal on a sphere or a plane, and only a rectangle in effect is hit).
+template <bool PIX>
+__global__ __launch_bounds__(kBlock) void ray_query_tree_kernel(RayQuery Q, QueryTree T) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= Q.n) return;
+  f3 o, d;
+  if (PIX) {
+    const int x = Q.xy[2 * i], y = Q.xy[2 * i + 1];
+    o = mk(Q.sc.cx, Q.sc.cy, Q.sc.cz);
+    d = primary_dir(Q.sc, (float)x / Q.sc.fW, (float)y / Q.sc.fH);
+  } else {
+    o = mk(Q.origins[3 * i], Q.origins[3 * i + 1], Q.origins[3 * i + 2]);
+    d = mk(Q.dirs[3 * i], Q.dirs[3 * i + 1], Q.dirs[3 * i + 2]);
+  }
+  float t;
+  const int ind = tree_closest(Q.sc, T, o, d, Q.thr, t);
+  if (Q.t) Q.t[i] = t;
+  if (Q.ind) Q.ind[i] = ind;
+  if (Q.nrm) {
+    f3 n = mk(0.0f, 0.0f, 0.0f);
+    if (ind >= 0) n = shape_normal_rc<true>(Q.sc.shapes[ind], __float_as_int(Q.sc.shapes[Q.sc.S + ind].w), o + t * d);
+    Q.nrm[3 * i] = n.x;
+    Q.nrm[3 * i + 1] = n.y;
+    Q.nrm[3 * i + 2] = n.z;
+  }
+  if (PIX && Q.dir_out) {
+    Q.dir_out[3 * i] = d.x;
+    Q.dir_out[3 * i + 1] = d.y;
+    Q.dir_out[3 * i + 2] = d.z;
+  }
+}
+
+// occluded_rc_kernel over the tree: shadow_ray's set-up as there, the plane table first, then the
+// always list, then the tree with the ray (np, l); out on the first occluder.  A culled ball's
+// members are spheres for which sphere_eval_shadow returns what shadow_occludes rejects:
+// sphere_eval_shadow forms pmc, b and del with the float operations of query_sphere (the ones the
+// proof's error bounds are about), returns -1 for a computed del < 0 (case (A)), and in case (B),
+// both roots negative by more than ten times their error, -1 again whichever of sqrt_rn_tail's
+// roots is taken (equal to sqrtf's above 2^-96, at most 2^-47 below); -1 > 0.0001 is false.
+__global__ __launch_bounds__(kBlock) void occluded_tree_kernel(QueryScene sc, QueryTree T, const float* __restrict__ from,
+                                                               const float* __restrict__ to, size_t n,
+                                                               unsigned char* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const f3 pos = mk(from[3 * i], from[3 * i + 1], from[3 * i + 2]);
+  const f3 lv = mk(to[3 * i], to[3 * i + 1], to[3 * i + 2]) - pos;
+  const f3 l = normalize(lv);
+  const float len = sqrtf(dot(lv, lv));
+  const f3 np = pos + 0.01f * l;
+  const double dlen = (double)len;
+  const float4* __restrict__ planes = sc.shapes + plane_table(sc.S);
+  const float4* __restrict__ rows = T.rows;
+  bool occ = false;
+  for (int k = 0; k < sc.nplanes && !occ; ++k)
+    occ = shadow_occludes(planar_eval<true>(planes, np, l, planes[2 * k], planes[2 * k + 1]), l, dlen);
+  for (int e = T.always_first; e < T.always_first + T.n_always && !occ; ++e)
+    occ = shadow_occludes(sphere_eval_shadow(np, l, rows[e]), l, dlen);
+  const bool gate = unit_gate(l);
+  const float4* __restrict__ nodes = T.nodes;
+  for (int k = 0; k < T.n_nodes && !occ;) {
+    const float4 cb = nodes[2 * k], lk = nodes[2 * k + 1];
+    if (tree_may_hit(gate, np, l, cb)) {
+      const int first = __float_as_int(lk.y), count = __float_as_int(lk.z);
+      for (int j = 0; j < count && !occ; ++j) occ = shadow_occludes(sphere_eval_shadow(np, l, rows[first + j]), l, dlen);
+      k = k + 1;
+    } else {
+      k = __float_as_int(lk.x);
+    }
+  }
+  out[i] = occ ? 1 : 0;
+}
+
 constexpr size_t kQueryMaxRays = (size_t)1 << 28;  // RT_QUERY_MAX_RAYS: the grid's x stays below 2^31
 
-hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream) {
+static bool has_tree(const QueryTree* tree) {
+  return tree && tree->n_nodes > 0 && tree->nodes && tree->rows && tree->index;
+}
+
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree) {
   if (q.n == 0) return hipSuccess;
   if (q.n > kQueryMaxRays || !q.sc.shapes || (!q.xy && (!q.origins || !q.dirs))) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((q.n + kBlock - 1) / kBlock));
+  if (has_tree(tree)) {
+    if (q.xy) hipLaunchKernelGGL(ray_query_tree_kernel<true>, grid, dim3(kBlock), 0, stream, q, *tree);
+    else hipLaunchKernelGGL(ray_query_tree_kernel<false>, grid, dim3(kBlock), 0, stream, q, *tree);
+    return hipGetLastError();
+  }
   const bool pl = q.sc.nplanes > 0;
   if (pl && q.sc.nrects > 0) {  // rectangles in effect: the RC twins
     if (q.xy) hipLaunchKernelGGL(ray_query_rc_kernel<true>, grid, dim3(kBlock), 0, stream, q);
@@ -3268,11 +3438,12 @@ hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream) {
 }
 
 hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
-                           hipStream_t stream) {
+                           hipStream_t stream, const QueryTree* tree) {
   if (n == 0) return hipSuccess;
   if (n > kQueryMaxRays || !sc.shapes || !from || !to || !out) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  if (sc.nplanes > 0 && sc.nrects > 0) hipLaunchKernelGGL(occluded_rc_kernel, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  if (has_tree(tree)) hipLaunchKernelGGL(occluded_tree_kernel, grid, dim3(kBlock), 0, stream, sc, *tree, from, to, n, out);
+  else if (sc.nplanes > 0 && sc.nrects > 0) hipLaunchKernelGGL(occluded_rc_kernel, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   else if (sc.nplanes > 0) hipLaunchKernelGGL(occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   else hipLaunchKernelGGL(occluded_kernel<false>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   return hipGetLastError();

@@ -123,6 +123,125 @@ int build_clusters(const Row* sph, int nobj, Row* ctab, unsigned long long* cmas
   return k;
 }
 
+// The ray queries' bounding-ball tree (include/rt/abi.h "Query tree"; the kernels: rt_kernels_impl.h
+// ray_query_tree_kernel).  Members as build_clusters takes them: the spheres among [0, nobj) with
+// finite geometry and |r| <= 8x the median |r|; the other spheres (a ground sphere, non-finite rows)
+// go to the always list, which every ray tests; NaN rows (no sphere) are left out.  Recursive median
+// splits of the members' centres along the widest axis, ties by index, down to leaves of at most
+// kTreeLeaf; the nodes in preorder, each with the index of the next node that is not below it, so a
+// traversal keeps no stack.  Every node stores a ball (centre, R):
+//   leaf:   |c_i - centre| + |r_i| <= R for every member (centre: the mean of the members' centres),
+//   inner:  |centre_child - centre| + R_child <= R for both children (centre and R: the smallest ball
+//           around the children's two balls),
+// R computed in binary64 from the stored binary32 centre and rounded up as build_clusters rounds its
+// radius.  By the triangle inequality every sphere below a node lies inside the node's ball, which is
+// all cluster_may_hit's proof asks of a ball.
+namespace {
+
+bool finite_row(const Row& g) { return std::isfinite(g.x) && std::isfinite(g.y) && std::isfinite(g.z) && std::isfinite(g.w); }
+float round_up(double R) { return std::nextafter((float)(R * (1.0 + 1e-6)), INFINITY); }
+double dist(const Row& a, double x, double y, double z) {
+  const double dx = (double)a.x - x, dy = (double)a.y - y, dz = (double)a.z - z;
+  return std::sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+// the subtree over members m[a, b); returns its node
+int tree_node(const Row* sph, std::vector<int>& m, int a, int b, QueryTreeHost& t) {
+  const int k = (int)t.ball.size();
+  t.ball.push_back(Row{});
+  t.link.push_back(TreeLink{});
+  if (b - a <= kTreeLeaf) {
+    std::sort(m.begin() + a, m.begin() + b);
+    double cx = 0, cy = 0, cz = 0;
+    for (int q = a; q < b; ++q) cx += sph[m[q]].x, cy += sph[m[q]].y, cz += sph[m[q]].z;
+    const float fx = (float)(cx / (b - a)), fy = (float)(cy / (b - a)), fz = (float)(cz / (b - a));
+    double R = 0.0;
+    const int first = (int)t.rows.size();
+    for (int q = a; q < b; ++q) {
+      const Row g = sph[m[q]];
+      R = std::max(R, dist(g, fx, fy, fz) + std::fabs((double)g.w));
+      t.rows.push_back(g);
+      t.index.push_back(m[q]);
+    }
+    t.ball[k] = Row{fx, fy, fz, round_up(R)};
+    t.link[k] = TreeLink{k + 1, first, b - a, 0};
+    t.n_leaves += 1;
+    return k;
+  }
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (int q = a; q < b; ++q) {
+    const Row g = sph[m[q]];
+    const double v[3] = {g.x, g.y, g.z};
+    for (int d = 0; d < 3; ++d) lo[d] = std::min(lo[d], v[d]), hi[d] = std::max(hi[d], v[d]);
+  }
+  int ax = 0;
+  for (int d = 1; d < 3; ++d)
+    if (hi[d] - lo[d] > hi[ax] - lo[ax]) ax = d;
+  const int mid = (a + b) / 2;
+  auto key = [&](int i) { const Row g = sph[i]; return ax == 0 ? g.x : ax == 1 ? g.y : g.z; };
+  std::nth_element(m.begin() + a, m.begin() + mid, m.begin() + b,
+                   [&](int i, int j) { return key(i) < key(j) || (key(i) == key(j) && i < j); });
+  const int l = tree_node(sph, m, a, mid, t);
+  const int r = tree_node(sph, m, mid, b, t);
+  // the smallest ball around the two children's: the larger one if it holds the other, else the
+  // ball on the segment through both centres
+  const Row A = t.ball[l], B = t.ball[r];
+  const double d = dist(A, B.x, B.y, B.z);
+  double cx, cy, cz;
+  if (d + B.w <= A.w || !(d > 0.0)) cx = A.x, cy = A.y, cz = A.z;
+  else if (d + A.w <= B.w) cx = B.x, cy = B.y, cz = B.z;
+  else {
+    const double s = 0.5 * (d + (double)B.w - (double)A.w) / d;  // from A's centre towards B's
+    cx = A.x + s * ((double)B.x - A.x), cy = A.y + s * ((double)B.y - A.y), cz = A.z + s * ((double)B.z - A.z);
+  }
+  if (!(std::isfinite(cx) && std::isfinite(cy) && std::isfinite(cz))) cx = A.x, cy = A.y, cz = A.z;  // (R overflowed)
+  const float fx = (float)cx, fy = (float)cy, fz = (float)cz;
+  const double R = std::max(dist(A, fx, fy, fz) + (double)A.w, dist(B, fx, fy, fz) + (double)B.w);
+  t.ball[k] = Row{fx, fy, fz, round_up(R)};
+  t.link[k] = TreeLink{(int)t.ball.size(), 0, 0, 0};
+  return k;
+}
+
+}  // namespace
+
+void QueryTreeHost::reserve(int num_shapes) {
+  const int n = num_shapes > 0 ? num_shapes : 0;
+  ball.reserve(tree_max_nodes(n));
+  link.reserve(tree_max_nodes(n));
+  rows.reserve(n);
+  index.reserve(n);
+}
+
+int build_query_tree(const Row* sph, int nobj, QueryTreeHost& t) {
+  t.ball.clear();
+  t.link.clear();
+  t.rows.clear();
+  t.index.clear();
+  t.n_leaf_entries = t.n_always = t.n_leaves = 0;
+  std::vector<float> radii;
+  for (int i = 0; i < nobj; ++i)
+    if (sph[i].x == sph[i].x && finite_row(sph[i])) radii.push_back(std::fabs(sph[i].w));
+  if ((int)radii.size() < 2 * kTreeLeaf) return 0;
+  std::nth_element(radii.begin(), radii.begin() + radii.size() / 2, radii.end());
+  const double big = 8.0 * radii[radii.size() / 2];
+  std::vector<int> members, always;
+  for (int i = 0; i < nobj; ++i) {
+    const Row g = sph[i];
+    if (g.x != g.x) continue;  // not a sphere (NaN row): never accepted
+    if (finite_row(g) && std::fabs(g.w) <= big) members.push_back(i);
+    else always.push_back(i);
+  }
+  if ((int)members.size() < 2 * kTreeLeaf) return 0;
+  tree_node(sph, members, 0, (int)members.size(), t);
+  t.n_leaf_entries = (int)t.rows.size();
+  for (int i : always) {
+    t.rows.push_back(sph[i]);
+    t.index.push_back(i);
+  }
+  t.n_always = (int)always.size();
+  return (int)t.ball.size();
+}
+
 int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& nplanes, int& ncl) {
   int nrects = 0;
   return pack_header(cfg, h, tab, nobj, nplanes, ncl, 0, nrects);
@@ -152,8 +271,12 @@ int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& 
     tab[(size_t)2 * Sc + i] = Row{s[16], s[17], s[18], s[19]};
     tab[(size_t)3 * Sc + i] = Row{s[4 + 3], s[12 + 3], 0.0f, 0.0f};
     // sphere table: the spheres' geometry; every other shape NaN (a NaN discriminant is never
-    // accepted: eval_ray's -1 for shapes it does not intersect, p_compute.glsl:121-138)
-    sph[i] = id == RT_SHAPE_SPHERE ? tab[i] : Row{qnan, qnan, qnan, qnan};
+    // accepted: eval_ray's -1 for shapes it does not intersect, p_compute.glsl:121-138).  A sphere
+    // whose radius is NaN has a NaN discriminant on every ray, so sphere_eval_ray returns NaN and
+    // neither a closest-hit scan nor a shadow ray ever takes it: it is packed as a NaN row too.  (With
+    // its finite centre kept, sphere_eval_shadow's v_max_f32 clamp, which returns the other operand
+    // for a NaN, went on with a root of 2^-50 and the sphere occluded what lay behind its centre.)
+    sph[i] = id == RT_SHAPE_SPHERE && s[3] == s[3] ? tab[i] : Row{qnan, qnan, qnan, qnan};
     if (i < nobj && id == RT_SHAPE_PLANE) {  // plane table: (normal, bits(index)), (p0, 0)
       Row a = Row{s[0], s[1], s[2], 0.0f};
       std::memcpy(&a.w, &i, 4);
@@ -233,3 +356,32 @@ int batch_slots(const unsigned char* same, int m, int prev, int nslots, int* slo
 }
 
 }  // namespace rt
+
+extern "C" int rt_query_tree_host(const rt_config* cfg, const void* header, size_t header_bytes, int flags, float* balls,
+                                  int32_t* links, int node_cap, float* leaf_rows, int32_t* leaf_index, int leaf_cap,
+                                  int32_t* always, int always_cap, int* n_leaf, int* n_always) {
+  if ((flags & ~RT_SCENE_RECTANGLES) != 0) return -1;
+  if (!cfg || !header || !balls || !links || !leaf_rows || !leaf_index || !always || node_cap < 0 || leaf_cap < 0 ||
+      always_cap < 0 || cfg->spp <= 0 || cfg->num_shapes < 0 ||
+      header_bytes != rt_header_bytes(cfg->num_shapes, cfg->spp))
+    return -1;
+  // the table an upload packs (pack_header: the sphere table), then the tree over it
+  const int Sc = rt::table_stride(*cfg);
+  std::vector<rt::Row> tab(rt::table_vec4_rect(Sc, cfg->spp));
+  int nobj = 0, np = 0, ncl = 0, nr = 0;
+  if (rt::pack_header(*cfg, (const float*)header, tab.data(), nobj, np, ncl, flags, nr) != RT_OK) return -1;
+  rt::QueryTreeHost t;
+  const int n = rt::build_query_tree(tab.data() + rt::sphere_table(Sc), nobj, t);
+  if (n > node_cap || t.n_leaf_entries > leaf_cap || t.n_always > always_cap) return -1;
+  if (n_leaf) *n_leaf = t.n_leaf_entries;
+  if (n_always) *n_always = t.n_always;
+  if (n == 0) return 0;
+  std::memcpy(balls, t.ball.data(), (size_t)n * sizeof(rt::Row));
+  std::memcpy(links, t.link.data(), (size_t)n * sizeof(rt::TreeLink));
+  std::memcpy(leaf_rows, t.rows.data(), (size_t)t.n_leaf_entries * sizeof(rt::Row));
+  std::memcpy(leaf_index, t.index.data(), (size_t)t.n_leaf_entries * sizeof(int));
+  std::memcpy(always, t.index.data() + t.n_leaf_entries, (size_t)t.n_always * sizeof(int));
+  if (n_leaf) *n_leaf = t.n_leaf_entries;
+  if (n_always) *n_always = t.n_always;
+  return n;
+}

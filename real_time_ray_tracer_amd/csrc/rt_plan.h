@@ -40,6 +40,31 @@ int pack_header(const rt_config& cfg, const float* h, Row* tab, int& nobj, int& 
 // Bounce-ray clusters of the sphere table `sph` (see rt_plan.cpp); returns the cluster count.
 int build_clusters(const Row* sph, int nobj, Row* ctab, unsigned long long* cmask);
 
+// The ray queries' bounding-ball tree over the spheres (include/rt/abi.h "Query tree"; rt_plan.cpp).
+// Leaves hold at most kTreeLeaf spheres: 4, the linear scan's rows per load (2 and 8 measured at 2048
+// spheres, DESIGN.md §5 "Round 18").
+#ifndef RT_TREE_LEAF
+#define RT_TREE_LEAF 4  // (A/B builds override it)
+#endif
+constexpr int kTreeLeaf = RT_TREE_LEAF;
+static_assert(kTreeLeaf >= 1, "a leaf holds at least one sphere");
+// Most nodes of a tree over n members: every leaf holds at least one, so at most n leaves.
+constexpr int tree_max_nodes(int n) { return n > 0 ? 2 * n - 1 : 0; }
+struct TreeLink {
+  int skip, first, count, pad;  // next node not below this one; a leaf's entries [first, first + count); an inner node: count 0
+};
+struct QueryTreeHost {
+  std::vector<Row> ball;       // [nodes] (centre, R), preorder
+  std::vector<TreeLink> link;  // [nodes]
+  std::vector<Row> rows;       // the leaf table: sphere rows in leaf order, then the always list's rows
+  std::vector<int> index;      // the entries' sphere indices
+  int n_leaf_entries = 0, n_always = 0, n_leaves = 0;
+  void reserve(int num_shapes);  // room for every tree over num_shapes rows: no build allocates afterwards
+};
+// Builds the tree of the sphere table `sph` over [0, nobj) into t; returns the node count, 0 = no tree
+// (fewer than 2 * kTreeLeaf members; t is then empty).
+int build_query_tree(const Row* sph, int nobj, QueryTreeHost& t);
+
 // The cull cache's key of a context configuration (rows resolved: row_begin < row_end) and header
 // h: the exact bytes of every input of the AO pool start's primary-ray cull (rt_cull.h) and the
 // launch's pool count.  Written to `out` when it fits in cap bytes; returns the key's size, 0 for a

@@ -16,11 +16,11 @@ struct QueryWork {
 
   // Closest hits of n rays of scene sc on st: the rays copied in, the kernel, the answers copied out
   // into whichever outputs are non-null, and a wait for st.  xy non-null: pixel rays (origins and
-  // dirs unused, dir_out the rays used); else the given rays.
-  int trace(const QueryScene& sc, const float* origins, const float* dirs, const int32_t* xy, size_t n, float thr,
+  // dirs unused, dir_out the rays used); else the given rays.  tree: the scene's query tree, or null.
+  int trace(const QueryScene& sc, const QueryTree* tree, const float* origins, const float* dirs, const int32_t* xy, size_t n, float thr,
             float* t, int32_t* ind, float* normals, float* dir_out, hipStream_t st, int& last_hip);
   // Occlusion of n segments, likewise.
-  int occluded(const QueryScene& sc, const float* from, const float* to, size_t n, uint8_t* out, hipStream_t st,
+  int occluded(const QueryScene& sc, const QueryTree* tree, const float* from, const float* to, size_t n, uint8_t* out, hipStream_t st,
                int& last_hip);
   void release();
 

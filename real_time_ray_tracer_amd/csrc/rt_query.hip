@@ -31,7 +31,7 @@ void QueryWork::release() {
   bytes = 0;
 }
 
-int QueryWork::trace(const QueryScene& sc, const float* origins, const float* dirs, const int32_t* xy, size_t n,
+int QueryWork::trace(const QueryScene& sc, const QueryTree* tree, const float* origins, const float* dirs, const int32_t* xy, size_t n,
                      float thr, float* t, int32_t* ind, float* normals, float* dir_out, hipStream_t st, int& last_hip) {
   const size_t v3 = part(n * 3 * sizeof(float)), v1 = part(n * sizeof(float));
   // inputs: origins | dirs, or xy;  outputs: t | ind | normals | dir_out (each only when asked for)
@@ -58,7 +58,7 @@ int QueryWork::trace(const QueryScene& sc, const float* origins, const float* di
   if (ind) q.ind = (int*)p, p += v1;
   if (normals) q.nrm = (float*)p, p += v3;
   if (xy && dir_out) q.dir_out = (float*)p, p += v3;
-  RT_HIP(last_hip, launch_ray_query(q, st));
+  RT_HIP(last_hip, launch_ray_query(q, st, tree));
   if (t) RT_HIP(last_hip, hipMemcpyAsync(t, q.t, n * sizeof(float), hipMemcpyDeviceToHost, st));
   if (ind) RT_HIP(last_hip, hipMemcpyAsync(ind, q.ind, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (normals) RT_HIP(last_hip, hipMemcpyAsync(normals, q.nrm, n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -67,7 +67,7 @@ int QueryWork::trace(const QueryScene& sc, const float* origins, const float* di
   return RT_OK;
 }
 
-int QueryWork::occluded(const QueryScene& sc, const float* from, const float* to, size_t n, uint8_t* out,
+int QueryWork::occluded(const QueryScene& sc, const QueryTree* tree, const float* from, const float* to, size_t n, uint8_t* out,
                         hipStream_t st, int& last_hip) {
   const size_t v3 = part(n * 3 * sizeof(float));
   int rc = reserve(2 * v3 + part(n), last_hip);
@@ -75,7 +75,7 @@ int QueryWork::occluded(const QueryScene& sc, const float* from, const float* to
   unsigned char* p = d_buf;
   RT_HIP(last_hip, hipMemcpyAsync(p, from, n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
   RT_HIP(last_hip, hipMemcpyAsync(p + v3, to, n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-  RT_HIP(last_hip, launch_occluded(sc, (const float*)p, (const float*)(p + v3), n, p + 2 * v3, st));
+  RT_HIP(last_hip, launch_occluded(sc, (const float*)p, (const float*)(p + v3), n, p + 2 * v3, st, tree));
   RT_HIP(last_hip, hipMemcpyAsync(out, p + 2 * v3, n, hipMemcpyDeviceToHost, st));
   RT_HIP(last_hip, hipStreamSynchronize(st));
   return RT_OK;

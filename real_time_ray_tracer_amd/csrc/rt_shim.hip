@@ -22,7 +22,7 @@
 // are those of the sequential order, bit for bit.
 //
 // The subsystems are components with their own state, operations and release() (rt_stage.h,
-// rt_sched.h, rt_cull.h, rt_gbuf.h, rt_timing.h, rt_query.h); the arithmetic that needs no HIP is rt_plan.cpp.
+// rt_sched.h, rt_cull.h, rt_gbuf.h, rt_timing.h, rt_query.h, rt_tree.h); the arithmetic that needs no HIP is rt_plan.cpp.
 // This file keeps the context, the launches and the entry points.
 #include <hip/hip_runtime.h>
 
@@ -42,6 +42,7 @@
 #include "rt_sched.h"
 #include "rt_stage.h"
 #include "rt_timing.h"
+#include "rt_tree.h"
 
 using rt::kAoStreams;
 using rt::kPipe;
@@ -77,6 +78,7 @@ struct rt_ctx {
   rt::GbufRing gbuf;        // pixels / normals / depth: F slots and pipe_depth more buffers each
   rt::LaunchTiming timing;  // rt_enable_timing
   rt::QueryWork query;      // the host-pointer ray queries' device workspace (made by the first such query)
+  rt::QueryTreeState tree;  // rt_set_query_tree: the queries' bounding-ball tree over the spheres (off: nothing)
   // pipelined mode 1
   bool pipelined = false;
   hipStream_t out_stream = nullptr, own_out_stream = nullptr;
@@ -151,6 +153,7 @@ void free_all(rt_ctx* c) {
   c->timing.release();
   c->gbuf.release();
   c->query.release();
+  c->tree.release();
   if (c->d_image_own) (void)hipFree(c->d_image_own);
   if (c->d_present_own) (void)hipFree(c->d_present_own);
   if (c->d_scaled_own) (void)hipFree(c->d_scaled_own);
@@ -223,6 +226,15 @@ int start_sequence(rt_ctx* c) {
   RT_HIP(c, hipEventRecord(c->ev_seq, c->stream));
   for (int k = 1; k < c->n_ao_streams; ++k) RT_HIP(c, hipStreamWaitEvent(c->ao_streams[k], c->ev_seq, 0));
   return RT_OK;
+}
+
+// The context has a new header (its packed table is c->table, its object count c->nobj): with the
+// query tree on, rebuild and upload it if the spheres changed.  On the main stream, where the
+// queries run.
+int tree_update(rt_ctx* c) {
+  if (!c->tree.on) return RT_OK;
+  return c->tree.update(rows(c->table.data()) + rt::sphere_table(table_stride(c)), c->nobj, c->stage, c->stream,
+                        c->last_hip);
 }
 
 const float* hv(const rt_ctx* c, int v) { return c->header.data() + 4 * v; }
@@ -661,7 +673,7 @@ int rt_upload_header(rt_ctx* c, const void* header, size_t bytes) {
   c->nrects = nr;
   c->ncl = ncl;
   c->have_header = true;
-  return RT_OK;
+  return tree_update(c);
 }
 
 int rt_upload_rand_buffer(rt_ctx* c, const float* rb, size_t n_vec4) {
@@ -849,6 +861,8 @@ int rt_compute_frames(rt_ctx* c, float* header, int mode, int frame, int n, uint
   }
   // the context is left as the per-frame calls would leave it: the last header, its table current
   std::memcpy(c->header.data(), header, bytes);
+  int tr = tree_update(c);  // (the frames' tables never went through rt_upload_header)
+  if (tr != RT_OK) return tr;
   return frame;
 }
 
@@ -897,6 +911,34 @@ int rt_set_rectangles(rt_ctx* c, int on) {
 }
 
 int rt_rectangles(rt_ctx* c) { return c ? (c->rectangles ? 1 : 0) : RT_E_INVAL; }
+
+int rt_set_query_tree(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  if (c->tree.on == (on != 0)) return RT_OK;
+  RT_HIP(c, hipSetDevice(c->device));
+  if (!on) {
+    int rc = drain(c);  // no query in flight reads the buffer freed here
+    if (rc != RT_OK) return rc;
+    streams_idle(c);
+    c->tree.release();
+    return RT_OK;
+  }
+  int rc = c->tree.enable(c->cfg.num_shapes, c->last_hip);
+  if (rc != RT_OK) return rc;
+  return c->have_header ? tree_update(c) : RT_OK;
+}
+
+int rt_query_tree(rt_ctx* c) { return c ? (c->tree.on ? 1 : 0) : RT_E_INVAL; }
+
+int rt_query_tree_stats(rt_ctx* c, int* nodes, int* leaves, int* always, size_t* bytes) {
+  if (!c) return RT_E_INVAL;
+  const bool built = c->tree.on && c->tree.n_nodes > 0;
+  if (nodes) *nodes = built ? c->tree.n_nodes : 0;
+  if (leaves) *leaves = built ? c->tree.host.n_leaves : 0;
+  if (always) *always = built ? c->tree.host.n_always : 0;
+  if (bytes) *bytes = c->tree.bytes;
+  return RT_OK;
+}
 
 int rt_tile_schedule_state(rt_ctx* c) {
   if (!c) return RT_E_INVAL;
@@ -1196,6 +1238,8 @@ static rt::QueryScene query_scene(const rt_ctx* c) {
   s.cx = cam[0]; s.cy = cam[1]; s.cz = cam[2];
   return s;
 }
+// the scene's query tree as a launch argument (v: where it is built), null when off or not built
+static const rt::QueryTree* query_tree(const rt_ctx* c, rt::QueryTree& v) { return c->tree.view(v); }
 static bool query_thr_ok(float thr) { return thr >= 0.0f && thr <= 3.402823466e+38f; }  // finite and >= 0; NaN fails
 // The checks every query starts with, then the main stream ordered behind everything the context
 // has enqueued (the pipelined streams joined with the context's own events: nothing is created).
@@ -1218,26 +1262,30 @@ int rt_trace_rays(rt_ctx* c, const float* origins, const float* dirs, size_t n, 
                   float* normals) {
   if (!query_thr_ok(thr)) return RT_E_INVAL;
   RT_QUERY_BEGIN(c, n, origins && dirs);
-  return c->query.trace(query_scene(c), origins, dirs, nullptr, n, thr, t, ind, normals, nullptr, c->stream, c->last_hip);
+  rt::QueryTree tv{};
+  return c->query.trace(query_scene(c), query_tree(c, tv), origins, dirs, nullptr, n, thr, t, ind, normals, nullptr, c->stream, c->last_hip);
 }
 
 int rt_trace_pixels(rt_ctx* c, const int32_t* xy, size_t n, float thr, float* t, int32_t* ind, float* normals,
                     float* dirs) {
   if (!query_thr_ok(thr)) return RT_E_INVAL;
   RT_QUERY_BEGIN(c, n, xy != nullptr);
-  return c->query.trace(query_scene(c), nullptr, nullptr, xy, n, thr, t, ind, normals, dirs, c->stream, c->last_hip);
+  rt::QueryTree tv{};
+  return c->query.trace(query_scene(c), query_tree(c, tv), nullptr, nullptr, xy, n, thr, t, ind, normals, dirs, c->stream, c->last_hip);
 }
 
 int rt_occluded(rt_ctx* c, const float* from, const float* to, size_t n, uint8_t* out) {
   RT_QUERY_BEGIN(c, n, from && to);
+  rt::QueryTree tv{};
   if (!out) return RT_OK;
-  return c->query.occluded(query_scene(c), from, to, n, out, c->stream, c->last_hip);
+  return c->query.occluded(query_scene(c), query_tree(c, tv), from, to, n, out, c->stream, c->last_hip);
 }
 
 int rt_trace_rays_device(rt_ctx* c, const void* d_origins, const void* d_dirs, size_t n, float thr, void* d_t,
                          void* d_ind, void* d_normals) {
   if (!query_thr_ok(thr)) return RT_E_INVAL;
   RT_QUERY_BEGIN(c, n, d_origins && d_dirs);
+  rt::QueryTree tv{};
   rt::RayQuery q{};
   q.sc = query_scene(c);
   q.origins = (const float*)d_origins;
@@ -1247,7 +1295,7 @@ int rt_trace_rays_device(rt_ctx* c, const void* d_origins, const void* d_dirs, s
   q.t = (float*)d_t;
   q.ind = (int*)d_ind;
   q.nrm = (float*)d_normals;
-  RT_HIP(c, rt::launch_ray_query(q, c->stream));
+  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv)));
   return RT_OK;
 }
 
@@ -1255,6 +1303,7 @@ int rt_trace_pixels_device(rt_ctx* c, const void* d_xy, size_t n, float thr, voi
                            void* d_dirs) {
   if (!query_thr_ok(thr)) return RT_E_INVAL;
   RT_QUERY_BEGIN(c, n, d_xy != nullptr);
+  rt::QueryTree tv{};
   rt::RayQuery q{};
   q.sc = query_scene(c);
   q.xy = (const int*)d_xy;
@@ -1264,15 +1313,16 @@ int rt_trace_pixels_device(rt_ctx* c, const void* d_xy, size_t n, float thr, voi
   q.ind = (int*)d_ind;
   q.nrm = (float*)d_normals;
   q.dir_out = (float*)d_dirs;
-  RT_HIP(c, rt::launch_ray_query(q, c->stream));
+  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv)));
   return RT_OK;
 }
 
 int rt_occluded_device(rt_ctx* c, const void* d_from, const void* d_to, size_t n, void* d_out) {
   RT_QUERY_BEGIN(c, n, d_from && d_to);
+  rt::QueryTree tv{};
   if (!d_out) return RT_OK;
   RT_HIP(c, rt::launch_occluded(query_scene(c), (const float*)d_from, (const float*)d_to, n, (unsigned char*)d_out,
-                                c->stream));
+                                c->stream, query_tree(c, tv)));
   return RT_OK;
 }
 
@@ -1413,10 +1463,11 @@ int rt_read_row_counters(rt_ctx* c, uint64_t* rows, int reset) {
 }
 
 int rt_selftest_math(rt_ctx* c, int fn, const float* in, float* out, size_t n) {
-  if (!c || !in || !out || fn < 0 || fn > RT_MATH_CULL_SHADOW) return RT_E_INVAL;
-  if (fn == RT_MATH_CULL_CLUSTER && n % 64 != 0) return RT_E_INVAL;  // its wave-mask form needs full waves
-  static const int in_w[] = {1, 2, 1, 2, 3, 10, 0, 0, 0, 0, 4, 0, 24, 28, 452, 14, 263},
-                   out_w[] = {1, 1, 1, 1, 3, 1, 1, 1, 1, 1, 5, 2, 7, 2, 320, 3, 128};
+  if (!c || !in || !out || fn < 0 || fn > RT_MATH_CULL_TREE) return RT_E_INVAL;
+  // RT_MATH_CULL_CLUSTER's wave-mask form needs full waves; RT_MATH_CULL_TREE takes its cases, under the same rule
+  if ((fn == RT_MATH_CULL_CLUSTER || fn == RT_MATH_CULL_TREE) && n % 64 != 0) return RT_E_INVAL;
+  static const int in_w[] = {1, 2, 1, 2, 3, 10, 0, 0, 0, 0, 4, 0, 24, 28, 452, 14, 263, 14},
+                   out_w[] = {1, 1, 1, 1, 3, 1, 1, 1, 1, 1, 5, 2, 7, 2, 320, 3, 128, 3};
   RT_HIP(c, hipSetDevice(c->device));
   float *din = nullptr, *dout = nullptr;
   const bool sweep = fn == RT_MATH_SQRT_SWEEP || fn == RT_MATH_RCP_SWEEP || fn == RT_MATH_SQRT_TAIL_SWEEP ||

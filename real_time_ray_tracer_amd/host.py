@@ -323,6 +323,24 @@ class Renderer:
         """Whether rectangles are intersected (rt_rectangles)."""
         return bool(self._c(self._lib.rt_rectangles(self.ctx), "rt_rectangles"))
 
+    def set_query_tree(self, on: bool):
+        """The ray queries over a tree of bounding balls around the spheres (rt_set_query_tree,
+        include/rt/abi.h "Query tree"; off by default).  The answers are the linear scan's, bit for bit."""
+        self._c(self._lib.rt_set_query_tree(self.ctx, int(bool(on))), "rt_set_query_tree")
+
+    @property
+    def query_tree(self) -> bool:
+        """Whether the ray queries walk the tree (rt_query_tree)."""
+        return bool(self._c(self._lib.rt_query_tree(self.ctx), "rt_query_tree"))
+
+    def query_tree_stats(self) -> dict:
+        """{"nodes", "leaves", "always", "bytes"} of the tree of the scene in effect and its device
+        buffer (rt_query_tree_stats); nodes 0: the scene has no tree, the queries scan."""
+        n, lv, a, b = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+        self._c(self._lib.rt_query_tree_stats(self.ctx, C.byref(n), C.byref(lv), C.byref(a), C.byref(b)),
+                "rt_query_tree_stats")
+        return {"nodes": n.value, "leaves": lv.value, "always": a.value, "bytes": b.value}
+
     @property
     def phong_gbuffer(self) -> bool:
         """Whether modes 3 and 4 write normals and depth (rt_phong_gbuffer)."""
@@ -550,10 +568,11 @@ class Renderer:
     def selftest_math(self, fn: int, inputs: np.ndarray, n: int) -> np.ndarray:
         out_w = {_lib.RT_MATH_NORMALIZE: 3, _lib.RT_MATH_SHADOW: 5, _lib.RT_MATH_SIN_TABLE: 2,
                  _lib.RT_MATH_CULL_CAMERA: 7, _lib.RT_MATH_CULL_PLANE: 2, _lib.RT_MATH_CULL_BOUNCE: 320,
-                 _lib.RT_MATH_CULL_CLUSTER: 3, _lib.RT_MATH_CULL_SHADOW: 128}.get(fn, 1)
+                 _lib.RT_MATH_CULL_CLUSTER: 3, _lib.RT_MATH_CULL_SHADOW: 128, _lib.RT_MATH_CULL_TREE: 3}.get(fn, 1)
         in_w = {_lib.RT_MATH_RANDOM: 2, _lib.RT_MATH_DIV: 2, _lib.RT_MATH_NORMALIZE: 3, _lib.RT_MATH_SPHERE: 10,
                 _lib.RT_MATH_SHADOW: 4, _lib.RT_MATH_CULL_CAMERA: 24, _lib.RT_MATH_CULL_PLANE: 28,
-                _lib.RT_MATH_CULL_BOUNCE: 452, _lib.RT_MATH_CULL_CLUSTER: 14, _lib.RT_MATH_CULL_SHADOW: 263}.get(fn, 1)
+                _lib.RT_MATH_CULL_BOUNCE: 452, _lib.RT_MATH_CULL_CLUSTER: 14, _lib.RT_MATH_CULL_SHADOW: 263,
+                _lib.RT_MATH_CULL_TREE: 14}.get(fn, 1)
         inp = np.ascontiguousarray(inputs, np.float32).reshape(-1)
         sweep = fn in (_lib.RT_MATH_SQRT_SWEEP, _lib.RT_MATH_RCP_SWEEP, _lib.RT_MATH_SQRT_TAIL_SWEEP,
                        _lib.RT_MATH_SIN_RANGE, _lib.RT_MATH_SIN_TABLE)
@@ -663,6 +682,11 @@ class StripGroup:
         """Renderer.set_rectangles on every strip (rt_group_set_rectangles); kept when the strips are
         re-created."""
         self._c(self._lib.rt_group_set_rectangles(self.g, int(bool(on))), "rt_group_set_rectangles")
+
+    def set_query_tree(self, on: bool):
+        """Renderer.set_query_tree on every strip (rt_group_set_query_tree); kept when the strips are
+        re-created."""
+        self._c(self._lib.rt_group_set_query_tree(self.g, int(bool(on))), "rt_group_set_query_tree")
 
     def bind_frame(self, device_ptr: int | None):
         self._c(self._lib.rt_group_bind_frame(self.g, C.c_void_p(device_ptr) if device_ptr else None),
@@ -800,6 +824,24 @@ def occluded_host(header: Header, a, b, rectangles: bool = False) -> np.ndarray:
                                            _lib.RT_SCENE_RECTANGLES if rectangles else 0,
                                            out.ctypes.data_as(C.c_void_p)), "rt_occluded_host_ex")
     return out.astype(bool)
+
+
+def query_tree_host(header: Header, rectangles: bool = False) -> dict:
+    """rt_query_tree_host (host only): the tree Renderer.set_query_tree builds for `header`:
+    {"balls" [n][4] float32 (centre, R), "links" [n][4] int32 (skip, first, count, 0), "leaf_rows"
+    [e][4] float32, "leaf_index" [e] int32, "always" [a] int32}; n = 0: no tree for this scene."""
+    S = max(header.S, 1)
+    balls, links = np.zeros((2 * S, 4), np.float32), np.zeros((2 * S, 4), np.int32)
+    rows, index, always = np.zeros((S, 4), np.float32), np.zeros(S, np.int32), np.zeros(S, np.int32)
+    e, a = C.c_int(), C.c_int()
+    n = _lib.load().rt_query_tree_host(C.byref(_query_cfg(header)), header.data.ctypes.data_as(C.c_void_p),
+                                       header.data.nbytes, _lib.RT_SCENE_RECTANGLES if rectangles else 0, fptr(balls),
+                                       _iptr(links), 2 * S, fptr(rows), _iptr(index), S, _iptr(always), S, C.byref(e),
+                                       C.byref(a))
+    if n < 0:
+        raise ValueError("rt_query_tree_host rejected the header")
+    return {"balls": balls[:n].copy(), "links": links[:n].copy(), "leaf_rows": rows[:e.value].copy(),
+            "leaf_index": index[:e.value].copy(), "always": always[:a.value].copy()}
 
 
 def plan_strips(row_cost, n: int) -> list[int]:
