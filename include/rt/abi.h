@@ -203,6 +203,26 @@ size_t rt_cull_cache_frame_bytes(rt_ctx* ctx);
 /* Test hook: this context's cap on the cull cache's bytes, in place of the build's 512 MiB
  * (0 restores it).  Before the first fill only. */
 int rt_debug_cull_cache_cap(rt_ctx* ctx, size_t bytes);
+/* Launch log (test hook, off by default).  While on, the context records the form of every kernel
+ * it launches, in launch order, at the point where its launcher picks the kernel: the render
+ * programs, the cull cache's fill, the ray queries, the 8-bit presents, the g-buffer layout
+ * conversion of rt_download / rt_upload_gbuffer and rt_selftest_math.  A form's name is the kernel
+ * template and its arguments, spelled as the library's demangled symbol after one normalisation:
+ * namespaces, the "void " return type and the parameter list stripped, "> >" written ">>"; for
+ * instance "ao_batch_kernel<AoProd<16, 20, 70u>>", "phong_rc_kernel<true, false>", "post_kernel".
+ * While off (on = 0, which also empties the log) a launch pays one untaken branch.
+ * rt_debug_launch_log_read: the names so far, each followed by '\n', NUL-terminated, into buf when
+ * they fit in cap bytes (then, with reset != 0, the log is emptied); returns the bytes needed, the
+ * NUL included, or a negative status.  buf may be NULL with cap 0 (a size query). */
+int rt_debug_launch_log(rt_ctx* ctx, int on);
+long long rt_debug_launch_log_read(rt_ctx* ctx, char* buf, size_t cap, int reset);
+/* Kernel forms: the AO programs' selector as the launcher calls it, for a launch of spp samples and
+ * depth D over a table of ncl bounce-ray clusters, nobj objects of which nplanes are planes
+ * (nrects of those rectangles in effect), with work counters, as a multi-frame launch, with a cull
+ * table.  out = (sppc, dc, flags) of the form "ao_batch_kernel<AoProd<sppc, dc, flagsu>>".  Never
+ * touches the GPU. */
+int rt_ao_form_host(int spp, int D, int ncl, int nobj, int nplanes, int nrects, int counters, int multi_frame,
+                    int cull_table, int out[3]);
 /* The cull cache's key of `header` (rt_header_bytes(num_shapes, spp) bytes) for a context created
  * with `cfg`: written to `key` when it fits in key_cap bytes (key may be NULL).  Returns the key's
  * size in bytes, 0 for an invalid configuration or header.  Two launches share a table iff their

@@ -78,6 +78,9 @@ SIGNATURES = {
     "rt_cull_cache_stats": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]),
     "rt_cull_cache_frame_bytes": (C.c_size_t, [_ctx]),
     "rt_debug_cull_cache_cap": (C.c_int, [_ctx, C.c_size_t]),
+    "rt_debug_launch_log": (C.c_int, [_ctx, C.c_int]),
+    "rt_debug_launch_log_read": (C.c_longlong, [_ctx, C.c_char_p, C.c_size_t, C.c_int]),
+    "rt_ao_form_host": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
     "rt_cull_key": (C.c_size_t, [C.POINTER(rt_config), _vp, C.c_size_t, _vp, C.c_size_t]),
     "rt_cluster_table": (C.c_int, [C.POINTER(rt_config), _vp, C.c_size_t, _fp, C.POINTER(C.c_uint64), C.c_int]),
     "rt_download": (C.c_int, [_ctx, _fp, _fp, _fp, _fp]),

@@ -54,6 +54,7 @@ struct CullCache {
   hipEvent_t ev_read[kAoStreams] = {};   // the last cached launches, one per reader stream
   int n_read = 0;                    // ev_read[0 .. n_read) are recorded and not yet waited for
   long long fills = 0, cached = 0;   // rt_cull_cache_stats
+  LaunchLog* log = nullptr;          // the context's launch log while it is on (rt_debug_launch_log)
 
   // Before an AO launch of p (its rows, tables and camera set) on st, of a context with
   // configuration cfg and header h: compare its key with the previous launch's and hand it the

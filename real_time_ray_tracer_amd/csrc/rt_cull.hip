@@ -80,7 +80,7 @@ int CullCache::before(const rt_config& cfg, const float* h, FrameParams& p, hipS
     if (!ev_fill) RT_HIP(last_hip, hipEventCreateWithFlags(&ev_fill, hipEventDisableTiming));
     for (int s = 0; s < n_read; ++s) RT_HIP(last_hip, hipStreamWaitEvent(st, ev_read[s], 0));
     n_read = 0;
-    RT_HIP(last_hip, launch_cull_fill(p, d_table, frame_bytes != 0, st));
+    RT_HIP(last_hip, launch_cull_fill(p, d_table, frame_bytes != 0, st, log));
     RT_HIP(last_hip, hipEventRecord(ev_fill, st));
     seen.clear();
     seen.s[0] = st;

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
+#include <vector>
+
 #include "rt_table.h"
 
 // Normals slot layout, shared by the kernels and the shim (rt_download_rect reads the slots
@@ -119,11 +122,21 @@ constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2
 
 enum KernelId { K_AOP = 1, K_POST = 2, K_AO = 3, K_PHONG = 4, K_HYBRID = 5 };
 
+// Launch log (rt_debug_launch_log, include/rt/abi.h "Launch log"): the kernels a context launched,
+// in launch order, each by its form's name: the kernel template and its arguments as the demangled
+// symbol spells them, without namespaces and parameter list ("ao_batch_kernel<AoProd<16, 20, 70u>>",
+// "phong_rc_kernel<true, false>", "post_kernel").  Every launcher below takes a log and appends the
+// name where it picks the kernel; nullptr (the default, and every context whose log is off): one
+// untaken branch per launch, no string is built.  Host code only.
+struct LaunchLog {
+  std::vector<std::string> names;
+};
+
 // Launch `program` (RT_PROG_* numbering) on `stream`.  Scenes with planes (p.nplanes > 0)
 // take the plane-testing instantiations, scenes with rectangles in effect (p.nrects > 0, counted in
 // p.nplanes too) their RC twins; every other shape is never hit (eval_ray returns -1 for it,
 // p_compute.glsl:121-138) and is skipped through the NaN entries of the sphere table.  Returns hipSuccess or the launch error.
-hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream);
+hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream, LaunchLog* log = nullptr);
 
 // Fill `table` ([ao_pool_count(p.trace_rows, p.W, p.spp)][(p.nobj + 63) / 64] u64) with the
 // primary-ray cull masks an AO launch of p computes per pool: the same device functions on the same
@@ -134,7 +147,8 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream)
 // own surviving spheres, and the frame is built on the hit's normal (a miss: on the reversed ray).
 // Same inputs as the masks, the same values from run to run; nothing computed from a frame
 // reaches a result, it only orders a pool's samples.
-hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream);
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream,
+                            LaunchLog* log = nullptr);
 
 // g-buffer layout conversion between the reference's [F][W][R] vec4 (x-major, y fastest:
 // src/main.cpp:49-85 over a context's R rows) and the device slots of one array kind (0 pixels:
@@ -146,13 +160,14 @@ struct GbufXfer {
   float4* ref;
   float4* slot[kMaxFrames];
 };
-hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream);
+hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream, LaunchLog* log = nullptr);
 
 // The blit into an 8-bit framebuffer (rt_present): `out` = [rows][W] RGBA8 (4-byte aligned) of
 // image = [rows][W] float4 by rt_quantize_rgba8's rule, output row j from image row j, or from row
 // rows - 1 - j when top_down.  Four pixels per lane and 16-byte stores when W % 4 == 0 and `out` is
 // 16-byte aligned, else one pixel per lane.
-hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream);
+hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream,
+                          LaunchLog* log = nullptr);
 
 // The blit at window size (rt_present_scaled): `out` = [out_h][out_w] RGBA8 (4-byte aligned) of
 // image = [R][W] float4 sampled bilinearly with clamped edges, by rt_resample_rgba8's rule; output
@@ -160,7 +175,7 @@ hipError_t launch_present(const float4* image, void* out, int W, int rows, int t
 // (hipErrorInvalidValue otherwise).  Four pixels per lane and 16-byte stores when out_w % 4 == 0 and
 // `out` is 16-byte aligned, else one pixel per lane.
 hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, int out_w, int out_h, int top_down,
-                                 hipStream_t stream);
+                                 hipStream_t stream, LaunchLog* log = nullptr);
 
 // Ray queries (include/rt/abi.h "Ray queries"): the scene and camera a query reads, as launch
 // arguments.  shapes: the base of a device table copy (rt_table.h).
@@ -205,13 +220,13 @@ struct QueryTree {
   int n_nodes, always_first, n_always;
 };
 // tree non-null with n_nodes > 0: ray_query_tree_kernel / occluded_tree_kernel, the same answers bit for bit
-hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree = nullptr);
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree = nullptr, LaunchLog* log = nullptr);
 // Occlusion of n segments from[i] -> to[i] ([n][3] each): out[i] = 1 when shadow_ray(pos = from[i],
 // light = to[i]) finds an occluder (p_compute.glsl:145-166), else 0.  Same instantiations and limits.
 hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
-                           hipStream_t stream, const QueryTree* tree = nullptr);
+                           hipStream_t stream, const QueryTree* tree = nullptr, LaunchLog* log = nullptr);
 
 // Device math self-test (rt_selftest_math).
-hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream);
+hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream, LaunchLog* log = nullptr);
 
 }  // namespace rt

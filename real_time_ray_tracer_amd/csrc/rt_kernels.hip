@@ -5,9 +5,9 @@
 
 namespace rt {
 
-hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream) {
+hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream, LaunchLog* log) {
   if (p.trace_rows <= 0) return hipSuccess;
-  return launch_production(program, p, launch_params(p), stream);
+  return launch_production(program, p, launch_params(p), stream, log);
 }
 
 }  // namespace rt

@@ -23,6 +23,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+
+#include "../../include/rt/abi.h"
 #include "rt_device.h"
 #include "rt_kernels.h"
 
@@ -2768,12 +2771,33 @@ __global__ __launch_bounds__(64) void cull_fill_kernel(FrameParams P, const floa
   }
 }
 
-hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream) {
+// The launch log's entry for the kernel a launcher is about to launch (rt_kernels.h LaunchLog; only
+// called with a log): the name as written, or built from the template arguments the launcher chose.
+inline void note_launch(LaunchLog* log, const char* name) { log->names.emplace_back(name); }
+template <class A0, class... A>
+inline void note_launch(LaunchLog* log, const char* fmt, A0 a0, A... a) {
+  char name[128];
+  snprintf(name, sizeof name, fmt, a0, a...);
+  log->names.emplace_back(name);
+}
+// hipLaunchKernelGGL(kernel, ...) with its log entry beside it: the name is written where the kernel
+// is, so a branch cannot log one form and launch another (tests/test_kernel_census_cpu.py holds the
+// names against the library's symbols)
+#define RT_LAUNCH(log, name, kernel, ...)    \
+  do {                                       \
+    if (log) note_launch(log, name);         \
+    hipLaunchKernelGGL(kernel, __VA_ARGS__); \
+  } while (0)
+#define RT_STR2(x) #x
+#define RT_STR(x) RT_STR2(x)
+#define RT_HYBW RT_STR(RT_HY_BW) ", " RT_STR(RT_HY_BW)  // kHyBW, kHyBW as a kernel name spells them
+
+hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream, LaunchLog* log) {
   const long long pools = ao_pool_count(p.trace_rows, p.W, p.spp);
   if (pools <= 0 || p.nobj <= 0) return hipSuccess;
   const float4* const sph = p.shapes + sphere_table(p.S);
-  if (frames) hipLaunchKernelGGL(cull_fill_kernel<true>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
-  else hipLaunchKernelGGL(cull_fill_kernel<false>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
+  if (frames) RT_LAUNCH(log, "cull_fill_kernel<true>", cull_fill_kernel<true>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
+  else RT_LAUNCH(log, "cull_fill_kernel<false>", cull_fill_kernel<false>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
   return hipGetLastError();
 }
 
@@ -2889,49 +2913,87 @@ inline void launch_ao(long long pools, hipStream_t stream, const FrameParams& q)
   hipLaunchKernelGGL((ao_batch_kernel<C>), g, dim3(64), (size_t)batch_lds<C>(q.spp, C::PTW ? 64 : q.nobj).total, stream,
                      q, q.sph, q.cull);
 }
-// AoChoice -> AoProd: the library holds exactly the configurations ao_select can return
+// The production form AoProd<SPPC, DC, FLAGS>, with its launch-log entry
+template <int SPPC, int DC, unsigned FLAGS>
+inline bool launch_ao_prod(long long pools, hipStream_t stream, const FrameParams& q, LaunchLog* log) {
+  if (log) note_launch(log, "ao_batch_kernel<AoProd<%d, %d, %uu>>", SPPC, DC, FLAGS);
+  launch_ao<AoProd<SPPC, DC, FLAGS>>(pools, stream, q);
+  return true;
+}
+// An all-sphere scene above kTailMaxObj spheres (AO_WIDE) has at least kB1SortMinObj, so a build
+// with the sort selects AO_SORT for it: the unsorted all-sphere shapes have no AO_WIDE forms there.
+// (RT_B1_SORT=0, make b1sort0, selects the unsorted ones for every scene and compiles them.)
+constexpr bool ao_shape_has_wide(unsigned shape) {
+  return (shape & (AO_PL | AO_SORT)) != 0 || !RT_B1_SORT || kB1SortMinObj > kTailMaxObj + 1;
+}
+// AoChoice -> AoProd.  The library holds exactly the configurations ao_select can return for a
+// scene the host can upload: tests/test_kernel_census_cpu.py compares the library's ao_batch_kernel
+// symbols with a sweep of the selector (rt_ao_form_host) and fails on a kernel no launch can reach.
+// Returns false, launching nothing, for flags that no form was compiled for.
 template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT | AO_CULLC
-inline void launch_ao_forms(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
-  switch (flags & (AO_WIDE | AO_CNT | AO_MF)) {
-    case 0: return launch_ao<AoProd<SPPC, DC, SHAPE>>(pools, stream, q);
-    case AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_CNT>>(pools, stream, q);
-    case AO_MF: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_MF>>(pools, stream, q);
-    case AO_WIDE: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE>>(pools, stream, q);
-    case AO_WIDE | AO_CNT: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_CNT>>(pools, stream, q);
-    case AO_WIDE | AO_MF: return launch_ao<AoProd<SPPC, DC, SHAPE | AO_WIDE | AO_MF>>(pools, stream, q);
+inline bool launch_ao_forms(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q, LaunchLog* log) {
+  if constexpr (ao_shape_has_wide(SHAPE)) {
+    switch (flags & (AO_WIDE | AO_CNT | AO_MF)) {
+      case AO_WIDE: return launch_ao_prod<SPPC, DC, SHAPE | AO_WIDE>(pools, stream, q, log);
+      case AO_WIDE | AO_CNT: return launch_ao_prod<SPPC, DC, SHAPE | AO_WIDE | AO_CNT>(pools, stream, q, log);
+      case AO_WIDE | AO_MF: return launch_ao_prod<SPPC, DC, SHAPE | AO_WIDE | AO_MF>(pools, stream, q, log);
+    }
   }
+  switch (flags & (AO_WIDE | AO_CNT | AO_MF)) {
+    case 0: return launch_ao_prod<SPPC, DC, SHAPE>(pools, stream, q, log);
+    case AO_CNT: return launch_ao_prod<SPPC, DC, SHAPE | AO_CNT>(pools, stream, q, log);
+    case AO_MF: return launch_ao_prod<SPPC, DC, SHAPE | AO_MF>(pools, stream, q, log);
+  }
+  return false;
 }
 template <int SPPC, int DC, unsigned SHAPE>  // SHAPE: the choice's AO_PL | AO_CLON | AO_SORT
-inline void launch_ao_shape(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q) {
+inline bool launch_ao_shape(unsigned flags, long long pools, hipStream_t stream, const FrameParams& q, LaunchLog* log) {
   if constexpr (!(SHAPE & AO_PL)) {
-    if (flags & AO_CULLC) return launch_ao_forms<SPPC, DC, SHAPE | AO_CULLC>(flags, pools, stream, q);
+    if (flags & AO_CULLC) return launch_ao_forms<SPPC, DC, SHAPE | AO_CULLC>(flags, pools, stream, q, log);
   }
-  launch_ao_forms<SPPC, DC, SHAPE>(flags, pools, stream, q);
+  return launch_ao_forms<SPPC, DC, SHAPE>(flags, pools, stream, q, log);
 }
 template <unsigned SORT>  // 0 or AO_SORT
-inline void launch_ao_choice(const AoChoice& c, long long pools, hipStream_t stream, const FrameParams& q) {
+inline bool launch_ao_choice(const AoChoice& c, long long pools, hipStream_t stream, const FrameParams& q, LaunchLog* log) {
   if (c.flags & AO_RC) {  // (with AO_PL)
     if constexpr (SORT == 0) {
-      if (c.sppc == 16) launch_ao_shape<16, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
-      else if (c.sppc == 4) launch_ao_shape<4, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
-      else launch_ao_shape<0, 0, AO_PL | AO_RC>(c.flags, pools, stream, q);
+      if (c.sppc == 16) return launch_ao_shape<16, 0, AO_PL | AO_RC>(c.flags, pools, stream, q, log);
+      else if (c.sppc == 4) return launch_ao_shape<4, 0, AO_PL | AO_RC>(c.flags, pools, stream, q, log);
+      else return launch_ao_shape<0, 0, AO_PL | AO_RC>(c.flags, pools, stream, q, log);
     }
   } else if (c.flags & AO_PL) {
     if constexpr (SORT == 0) {
-      if (c.sppc == 16) launch_ao_shape<16, 0, AO_PL>(c.flags, pools, stream, q);
-      else if (c.sppc == 4) launch_ao_shape<4, 0, AO_PL>(c.flags, pools, stream, q);
-      else launch_ao_shape<0, 0, AO_PL>(c.flags, pools, stream, q);
+      if (c.sppc == 16) return launch_ao_shape<16, 0, AO_PL>(c.flags, pools, stream, q, log);
+      else if (c.sppc == 4) return launch_ao_shape<4, 0, AO_PL>(c.flags, pools, stream, q, log);
+      else return launch_ao_shape<0, 0, AO_PL>(c.flags, pools, stream, q, log);
     }
   } else if (c.flags & AO_CLON) {
-    if (c.sppc == 16) launch_ao_shape<16, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q);
-    else launch_ao_shape<64, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q);
+    if (c.sppc == 16) return launch_ao_shape<16, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q, log);
+    else return launch_ao_shape<64, kRefDepth, AO_CLON | SORT>(c.flags, pools, stream, q, log);
   } else {
-    if (c.sppc == 16) launch_ao_shape<16, 0, SORT>(c.flags, pools, stream, q);
-    else if (c.sppc == 64) launch_ao_shape<64, 0, SORT>(c.flags, pools, stream, q);
-    else if (c.sppc == 4) launch_ao_shape<4, 0, SORT>(c.flags, pools, stream, q);
-    else launch_ao_shape<0, 0, SORT>(c.flags, pools, stream, q);
+    if (c.sppc == 16) return launch_ao_shape<16, 0, SORT>(c.flags, pools, stream, q, log);
+    else if (c.sppc == 64) return launch_ao_shape<64, 0, SORT>(c.flags, pools, stream, q, log);
+    else if (c.sppc == 4) return launch_ao_shape<4, 0, SORT>(c.flags, pools, stream, q, log);
+    else return launch_ao_shape<0, 0, SORT>(c.flags, pools, stream, q, log);
   }
+  return false;
 }
+
+}  // namespace rt
+
+// The selector as a host entry point (include/rt/abi.h "Kernel forms"): ao_select itself, for the
+// census tests.  Touches no GPU.
+extern "C" int rt_ao_form_host(int spp, int D, int ncl, int nobj, int nplanes, int nrects, int counters, int multi_frame,
+                               int cull_table, int out[3]) {
+  if (!out) return RT_E_INVAL;
+  const rt::AoChoice c = rt::ao_select(spp, D, ncl, nobj, nplanes, nrects, counters != 0, multi_frame != 0, cull_table != 0);
+  out[0] = c.sppc;
+  out[1] = c.dc;
+  out[2] = (int)c.flags;
+  return RT_OK;
+}
+
+namespace rt {
 
 // g-buffer layout conversion (rt_download / rt_upload_gbuffer, the host-buffer path of
 // compute_one_shader / compute_two_shaders): one thread per reference vec4, reference side
@@ -2956,10 +3018,10 @@ __global__ __launch_bounds__(256) void gbuf_convert_kernel(GbufXfer x) {
   }
 }
 
-hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream) {
+hipError_t launch_gbuf_convert(const GbufXfer& x, hipStream_t stream, LaunchLog* log) {
   const size_t total = (size_t)x.F * x.W * x.R;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(gbuf_convert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x);
+  RT_LAUNCH(log, "gbuf_convert_kernel", gbuf_convert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x);
   return hipGetLastError();
 }
 
@@ -2998,12 +3060,12 @@ __global__ __launch_bounds__(256) void present_kernel(const float4* __restrict__
   }
 }
 
-hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream) {
+hipError_t launch_present(const float4* image, void* out, int W, int rows, int top_down, hipStream_t stream, LaunchLog* log) {
   if (W <= 0 || rows <= 0) return hipSuccess;
   const int wide = W % 4 == 0 && ((uintptr_t)out & 15) == 0;
   const int units = wide ? W / 4 : W;
-  hipLaunchKernelGGL(present_kernel, dim3((unsigned)((units + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535)),
-                     dim3(256), 0, stream, image, (unsigned*)out, W, rows, top_down, wide);
+  RT_LAUNCH(log, "present_kernel", present_kernel, dim3((unsigned)((units + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535)),
+            dim3(256), 0, stream, image, (unsigned*)out, W, rows, top_down, wide);
   return hipGetLastError();
 }
 
@@ -3090,7 +3152,7 @@ __global__ __launch_bounds__(256) void present_scaled_kernel(const float4* __res
 constexpr int kScaledBlocks = RT_SCALED_BLOCKS;
 constexpr int kScaledMax = 16384;  // RT_PRESENT_SCALED_MAX: the tap arithmetic is 32-bit
 hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, int out_w, int out_h, int top_down,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, LaunchLog* log) {
   if (!image || !out || W < 1 || R < 1 || out_w < 1 || out_h < 1 || W > kScaledMax || R > kScaledMax ||
       out_w > kScaledMax || out_h > kScaledMax || ((uintptr_t)out & 3))
     return hipErrorInvalidValue;
@@ -3099,7 +3161,7 @@ hipError_t launch_present_scaled(const float4* image, int W, int R, void* out, i
   const int gx = (units + 255) / 256;
   const int per = kScaledBlocks / gx > 0 ? kScaledBlocks / gx : 1;
   const int gy = out_h < per ? out_h : per;
-  hipLaunchKernelGGL(present_scaled_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, stream, image, W, R,
+  RT_LAUNCH(log, "present_scaled_kernel", present_scaled_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, stream, image, W, R,
                      (unsigned*)out, out_w, out_h, top_down, wide);
   return hipGetLastError();
 }
@@ -3412,40 +3474,40 @@ static bool has_tree(const QueryTree* tree) {
   return tree && tree->n_nodes > 0 && tree->nodes && tree->rows && tree->index;
 }
 
-hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree) {
+hipError_t launch_ray_query(const RayQuery& q, hipStream_t stream, const QueryTree* tree, LaunchLog* log) {
   if (q.n == 0) return hipSuccess;
   if (q.n > kQueryMaxRays || !q.sc.shapes || (!q.xy && (!q.origins || !q.dirs))) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((q.n + kBlock - 1) / kBlock));
   if (has_tree(tree)) {
-    if (q.xy) hipLaunchKernelGGL(ray_query_tree_kernel<true>, grid, dim3(kBlock), 0, stream, q, *tree);
-    else hipLaunchKernelGGL(ray_query_tree_kernel<false>, grid, dim3(kBlock), 0, stream, q, *tree);
+    if (q.xy) RT_LAUNCH(log, "ray_query_tree_kernel<true>", ray_query_tree_kernel<true>, grid, dim3(kBlock), 0, stream, q, *tree);
+    else RT_LAUNCH(log, "ray_query_tree_kernel<false>", ray_query_tree_kernel<false>, grid, dim3(kBlock), 0, stream, q, *tree);
     return hipGetLastError();
   }
   const bool pl = q.sc.nplanes > 0;
   if (pl && q.sc.nrects > 0) {  // rectangles in effect: the RC twins
-    if (q.xy) hipLaunchKernelGGL(ray_query_rc_kernel<true>, grid, dim3(kBlock), 0, stream, q);
-    else hipLaunchKernelGGL(ray_query_rc_kernel<false>, grid, dim3(kBlock), 0, stream, q);
+    if (q.xy) RT_LAUNCH(log, "ray_query_rc_kernel<true>", ray_query_rc_kernel<true>, grid, dim3(kBlock), 0, stream, q);
+    else RT_LAUNCH(log, "ray_query_rc_kernel<false>", ray_query_rc_kernel<false>, grid, dim3(kBlock), 0, stream, q);
     return hipGetLastError();
   }
   if (q.xy) {
-    if (pl) hipLaunchKernelGGL((ray_query_kernel<true, true>), grid, dim3(kBlock), 0, stream, q);
-    else hipLaunchKernelGGL((ray_query_kernel<false, true>), grid, dim3(kBlock), 0, stream, q);
+    if (pl) RT_LAUNCH(log, "ray_query_kernel<true, true>", (ray_query_kernel<true, true>), grid, dim3(kBlock), 0, stream, q);
+    else RT_LAUNCH(log, "ray_query_kernel<false, true>", (ray_query_kernel<false, true>), grid, dim3(kBlock), 0, stream, q);
   } else {
-    if (pl) hipLaunchKernelGGL((ray_query_kernel<true, false>), grid, dim3(kBlock), 0, stream, q);
-    else hipLaunchKernelGGL((ray_query_kernel<false, false>), grid, dim3(kBlock), 0, stream, q);
+    if (pl) RT_LAUNCH(log, "ray_query_kernel<true, false>", (ray_query_kernel<true, false>), grid, dim3(kBlock), 0, stream, q);
+    else RT_LAUNCH(log, "ray_query_kernel<false, false>", (ray_query_kernel<false, false>), grid, dim3(kBlock), 0, stream, q);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_occluded(const QueryScene& sc, const float* from, const float* to, size_t n, unsigned char* out,
-                           hipStream_t stream, const QueryTree* tree) {
+                           hipStream_t stream, const QueryTree* tree, LaunchLog* log) {
   if (n == 0) return hipSuccess;
   if (n > kQueryMaxRays || !sc.shapes || !from || !to || !out) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  if (has_tree(tree)) hipLaunchKernelGGL(occluded_tree_kernel, grid, dim3(kBlock), 0, stream, sc, *tree, from, to, n, out);
-  else if (sc.nplanes > 0 && sc.nrects > 0) hipLaunchKernelGGL(occluded_rc_kernel, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
-  else if (sc.nplanes > 0) hipLaunchKernelGGL(occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
-  else hipLaunchKernelGGL(occluded_kernel<false>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  if (has_tree(tree)) RT_LAUNCH(log, "occluded_tree_kernel", occluded_tree_kernel, grid, dim3(kBlock), 0, stream, sc, *tree, from, to, n, out);
+  else if (sc.nplanes > 0 && sc.nrects > 0) RT_LAUNCH(log, "occluded_rc_kernel", occluded_rc_kernel, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  else if (sc.nplanes > 0) RT_LAUNCH(log, "occluded_kernel<true>", occluded_kernel<true>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
+  else RT_LAUNCH(log, "occluded_kernel<false>", occluded_kernel<false>, grid, dim3(kBlock), 0, stream, sc, from, to, n, out);
   return hipGetLastError();
 }
 
@@ -3484,7 +3546,8 @@ inline FrameParams launch_params(const FrameParams& p) {
   return q;
 }
 
-inline hipError_t launch_production(int program, const FrameParams& p, const FrameParams& q, hipStream_t stream) {
+inline hipError_t launch_production(int program, const FrameParams& p, const FrameParams& q, hipStream_t stream,
+                                    LaunchLog* log = nullptr) {
   const bool pl = p.nplanes > 0;
   if (program == K_AOP || program == K_AO) {
     const long long npix = (long long)p.trace_rows * p.W;
@@ -3493,9 +3556,9 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.nrects, p.counters || p.row_counters,
                                  p.mf_n > 0, q.cull != nullptr);
     // (kSortBit: a build with RT_B1_SORT=0 never selects the sort and compiles no SORT instantiation)
-    if (c.flags & AO_SORT) launch_ao_choice<kSortBit>(c, pools, stream, q);
-    else launch_ao_choice<0>(c, pools, stream, q);
-    return hipGetLastError();
+    const bool launched = (c.flags & AO_SORT) ? launch_ao_choice<kSortBit>(c, pools, stream, q, log)
+                                              : launch_ao_choice<0>(c, pools, stream, q, log);
+    return launched ? hipGetLastError() : hipErrorInvalidValue;  // (no compiled form: an error, not a silent skip)
   }
   // modes 3/4 multi-frame launches: FPB frames per block (block_frames)
   const int fpb = program == K_PHONG ? kPhongFramesPerBlock : kHybridFramesPerBlock;
@@ -3510,47 +3573,47 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
   if (pl && p.nrects > 0 && (program == K_PHONG || program == K_HYBRID)) {  // rectangles in effect: the RC twins
     const bool gb = p.phong_gbuf != 0;
     if (program == K_PHONG) {
-      if (mf && gb) hipLaunchKernelGGL((phong_rc_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (mf) hipLaunchKernelGGL((phong_rc_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (gb) hipLaunchKernelGGL((phong_rc_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else hipLaunchKernelGGL((phong_rc_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      if (mf && gb) RT_LAUNCH(log, "phong_rc_kernel<true, true>", (phong_rc_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (mf) RT_LAUNCH(log, "phong_rc_kernel<true, false>", (phong_rc_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (gb) RT_LAUNCH(log, "phong_rc_kernel<false, true>", (phong_rc_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else RT_LAUNCH(log, "phong_rc_kernel<false, false>", (phong_rc_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
     } else {
-      if (mf && gb) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, true, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (mf) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, true, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (gb) hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, false, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else hipLaunchKernelGGL((hybrid_rc_kernel<kHyBW, kHyBW, false, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      if (mf && gb) RT_LAUNCH(log, "hybrid_rc_kernel<" RT_HYBW ", true, true>", (hybrid_rc_kernel<kHyBW, kHyBW, true, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (mf) RT_LAUNCH(log, "hybrid_rc_kernel<" RT_HYBW ", true, false>", (hybrid_rc_kernel<kHyBW, kHyBW, true, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (gb) RT_LAUNCH(log, "hybrid_rc_kernel<" RT_HYBW ", false, true>", (hybrid_rc_kernel<kHyBW, kHyBW, false, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else RT_LAUNCH(log, "hybrid_rc_kernel<" RT_HYBW ", false, false>", (hybrid_rc_kernel<kHyBW, kHyBW, false, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
     }
     return hipGetLastError();
   }
   if (p.phong_gbuf && (program == K_PHONG || program == K_HYBRID)) {  // rt_set_phong_gbuffer: the GB instantiations
     if (program == K_PHONG) {
-      if (pl && mf) hipLaunchKernelGGL((phong_gbuf_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (pl) hipLaunchKernelGGL((phong_gbuf_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (mf) hipLaunchKernelGGL((phong_gbuf_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else hipLaunchKernelGGL((phong_gbuf_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      if (pl && mf) RT_LAUNCH(log, "phong_gbuf_kernel<true, true>", (phong_gbuf_kernel<true, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (pl) RT_LAUNCH(log, "phong_gbuf_kernel<true, false>", (phong_gbuf_kernel<true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (mf) RT_LAUNCH(log, "phong_gbuf_kernel<false, true>", (phong_gbuf_kernel<false, true>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else RT_LAUNCH(log, "phong_gbuf_kernel<false, false>", (phong_gbuf_kernel<false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
     } else {
-      if (pl && mf) hipLaunchKernelGGL((hybrid_gbuf_kernel<true, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (pl) hipLaunchKernelGGL((hybrid_gbuf_kernel<true, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (mf) hipLaunchKernelGGL((hybrid_gbuf_kernel<false, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else hipLaunchKernelGGL((hybrid_gbuf_kernel<false, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      if (pl && mf) RT_LAUNCH(log, "hybrid_gbuf_kernel<true, " RT_HYBW ", true>", (hybrid_gbuf_kernel<true, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (pl) RT_LAUNCH(log, "hybrid_gbuf_kernel<true, " RT_HYBW ", false>", (hybrid_gbuf_kernel<true, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (mf) RT_LAUNCH(log, "hybrid_gbuf_kernel<false, " RT_HYBW ", true>", (hybrid_gbuf_kernel<false, kHyBW, kHyBW, true>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else RT_LAUNCH(log, "hybrid_gbuf_kernel<false, " RT_HYBW ", false>", (hybrid_gbuf_kernel<false, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
     }
     return hipGetLastError();
   }
   switch (program) {
     case K_PHONG:
-      if (pl && mf) hipLaunchKernelGGL((phong_kernel<true, true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (pl) hipLaunchKernelGGL((phong_kernel<true, true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else if (mf) hipLaunchKernelGGL((phong_kernel<true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
-      else hipLaunchKernelGGL((phong_kernel<true, false, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      if (pl && mf) RT_LAUNCH(log, "phong_kernel<true, true, false, true>", (phong_kernel<true, true, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (pl) RT_LAUNCH(log, "phong_kernel<true, true, false, false>", (phong_kernel<true, true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else if (mf) RT_LAUNCH(log, "phong_kernel<true, false, false, true>", (phong_kernel<true, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
+      else RT_LAUNCH(log, "phong_kernel<true, false, false, false>", (phong_kernel<true, false, false, false>), grid, dim3(kBlock), 0, stream, q.sph, q.shapes, q);
       break;
     case K_HYBRID:
-      if (pl && mf) hipLaunchKernelGGL((hybrid_kernel<true, true, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (pl) hipLaunchKernelGGL((hybrid_kernel<true, true, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else if (mf) hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
-      else hipLaunchKernelGGL((hybrid_kernel<true, false, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      if (pl && mf) RT_LAUNCH(log, "hybrid_kernel<true, true, false, 0, " RT_HYBW ", true>", (hybrid_kernel<true, true, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (pl) RT_LAUNCH(log, "hybrid_kernel<true, true, false, 0, " RT_HYBW ", false>", (hybrid_kernel<true, true, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else if (mf) RT_LAUNCH(log, "hybrid_kernel<true, false, false, 0, " RT_HYBW ", true>", (hybrid_kernel<true, false, false, 0, kHyBW, kHyBW>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
+      else RT_LAUNCH(log, "hybrid_kernel<true, false, false, 0, " RT_HYBW ", false>", (hybrid_kernel<true, false, false, 0, kHyBW, kHyBW, false>), grid, hyb, 0, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
       break;
     case K_POST:
-      hipLaunchKernelGGL(post_kernel,
+      RT_LAUNCH(log, "post_kernel", post_kernel,
                          dim3((p.W + kPostTileW - 1) / kPostTileW, (p.trace_rows + kPostTileH - 1) / kPostTileH),
                          dim3(kBlock), 0, stream, q);
       break;
@@ -3560,11 +3623,11 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
   return hipGetLastError();
 }
 
-hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream) {
+hipError_t launch_selftest(int fn, const float* d_in, float* d_out, size_t n, hipStream_t stream, LaunchLog* log) {
   if (n == 0) return hipSuccess;
   const size_t lanes = selftest_wave_fn(fn) ? n * 64 : n;
   unsigned grid = (unsigned)((lanes + 255) / 256);
-  hipLaunchKernelGGL(selftest_kernel, dim3(grid), dim3(256), 0, stream, fn, d_in, d_out, n);
+  RT_LAUNCH(log, "selftest_kernel", selftest_kernel, dim3(grid), dim3(256), 0, stream, fn, d_in, d_out, n);
   return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@ struct QueryWork {
   unsigned char* d_buf = nullptr;
   size_t bytes = 0;
   long long grows = 0;  // allocations so far (the first included)
+  LaunchLog* log = nullptr;  // the context's launch log while it is on (rt_debug_launch_log)
 
   // Closest hits of n rays of scene sc on st: the rays copied in, the kernel, the answers copied out
   // into whichever outputs are non-null, and a wait for st.  xy non-null: pixel rays (origins and

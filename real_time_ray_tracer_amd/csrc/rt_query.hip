@@ -58,7 +58,7 @@ int QueryWork::trace(const QueryScene& sc, const QueryTree* tree, const float* o
   if (ind) q.ind = (int*)p, p += v1;
   if (normals) q.nrm = (float*)p, p += v3;
   if (xy && dir_out) q.dir_out = (float*)p, p += v3;
-  RT_HIP(last_hip, launch_ray_query(q, st, tree));
+  RT_HIP(last_hip, launch_ray_query(q, st, tree, log));
   if (t) RT_HIP(last_hip, hipMemcpyAsync(t, q.t, n * sizeof(float), hipMemcpyDeviceToHost, st));
   if (ind) RT_HIP(last_hip, hipMemcpyAsync(ind, q.ind, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (normals) RT_HIP(last_hip, hipMemcpyAsync(normals, q.nrm, n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -75,7 +75,7 @@ int QueryWork::occluded(const QueryScene& sc, const QueryTree* tree, const float
   unsigned char* p = d_buf;
   RT_HIP(last_hip, hipMemcpyAsync(p, from, n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
   RT_HIP(last_hip, hipMemcpyAsync(p + v3, to, n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-  RT_HIP(last_hip, launch_occluded(sc, (const float*)p, (const float*)(p + v3), n, p + 2 * v3, st, tree));
+  RT_HIP(last_hip, launch_occluded(sc, (const float*)p, (const float*)(p + v3), n, p + 2 * v3, st, tree, log));
   RT_HIP(last_hip, hipMemcpyAsync(out, p + 2 * v3, n, hipMemcpyDeviceToHost, st));
   RT_HIP(last_hip, hipStreamSynchronize(st));
   return RT_OK;

@@ -123,6 +123,10 @@ struct rt_ctx {
   bool counting = false;
   bool row_counting = false;
   int last_hip = 0;
+  // rt_debug_launch_log: the forms launched while the log is on, in order; `log` is &launch_log then,
+  // else nullptr (and so are cull.log and query.log): what every launcher is handed
+  rt::LaunchLog launch_log;
+  rt::LaunchLog* log = nullptr;
 };
 
 namespace {
@@ -285,7 +289,7 @@ int launch_timed(rt_ctx* c, int program, const rt::FrameParams& p, hipStream_t s
     int rc = t.begin(pair, st, c->last_hip);
     if (rc != RT_OK) return rc;
   }
-  RT_HIP(c, rt::launch_program(program, p, st));
+  RT_HIP(c, rt::launch_program(program, p, st, c->log));
   if (p.image) c->img_stream = st;  // consumers of the image order their reads after this stream
   return t.on ? t.end(program, pair, st, c->last_hip) : RT_OK;
 }
@@ -965,6 +969,32 @@ int rt_debug_cull_cache_cap(rt_ctx* c, size_t bytes) {
 
 size_t rt_cull_cache_frame_bytes(rt_ctx* c) { return c ? c->cull.frame_bytes : 0; }
 
+int rt_debug_launch_log(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  c->log = on ? &c->launch_log : nullptr;
+  c->cull.log = c->log;
+  c->query.log = c->log;
+  if (!on) c->launch_log.names.clear();
+  return RT_OK;
+}
+
+long long rt_debug_launch_log_read(rt_ctx* c, char* buf, size_t cap, int reset) {
+  if (!c || (!buf && cap)) return RT_E_INVAL;
+  size_t need = 1;  // the terminating NUL
+  for (const auto& s : c->launch_log.names) need += s.size() + 1;
+  if (need <= cap) {
+    char* p = buf;
+    for (const auto& s : c->launch_log.names) {
+      std::memcpy(p, s.data(), s.size());
+      p += s.size();
+      *p++ = '\n';
+    }
+    *p = 0;
+    if (reset) c->launch_log.names.clear();
+  }
+  return (long long)need;
+}
+
 int rt_cull_cache_stats(rt_ctx* c, long long* fills, long long* cached_launches, size_t* table_bytes) {
   if (!c) return RT_E_INVAL;
   if (fills) *fills = c->cull.fills;
@@ -1015,7 +1045,7 @@ int rt_download(rt_ctx* c, float* pixels, float* normals, float* depth, float* i
   for (int k = 0; k < 3; ++k) {
     if (!dst[k]) continue;
     for (int f = 0; f < c->cfg.num_frames; ++f) {  // stream order: frame f's copy precedes f+1's convert
-      RT_HIP(c, rt::launch_gbuf_convert(xfer_desc(c, k, 1, f), c->stream));
+      RT_HIP(c, rt::launch_gbuf_convert(xfer_desc(c, k, 1, f), c->stream, c->log));
       RT_HIP(c, hipMemcpyAsync((char*)dst[k] + (size_t)f * fbytes, c->d_xfer, fbytes, hipMemcpyDeviceToHost,
                                c->stream));
     }
@@ -1093,7 +1123,7 @@ int rt_upload_gbuffer(rt_ctx* c, const float* pixels, const float* normals, cons
     for (int f = 0; f < c->cfg.num_frames; ++f) {
       RT_HIP(c, hipMemcpyAsync(c->d_xfer, (const char*)src[k] + (size_t)f * fbytes, fbytes, hipMemcpyHostToDevice,
                                c->stream));
-      RT_HIP(c, rt::launch_gbuf_convert(xfer_desc(c, k, 0, f), c->stream));
+      RT_HIP(c, rt::launch_gbuf_convert(xfer_desc(c, k, 0, f), c->stream, c->log));
     }
   }
   RT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1125,7 +1155,7 @@ int rt_present(rt_ctx* c, int top_down) {
     }
     dst = c->d_present_own;
   }
-  RT_HIP(c, rt::launch_present(c->d_image, dst, c->cfg.width, c->own_rows, top_down != 0, st));
+  RT_HIP(c, rt::launch_present(c->d_image, dst, c->cfg.width, c->own_rows, top_down != 0, st, c->log));
   c->d_present = dst;
   return RT_OK;
 }
@@ -1184,7 +1214,7 @@ int rt_present_scaled(rt_ctx* c, int out_width, int out_height, int top_down) {
     dst = c->d_scaled_own;
   }
   RT_HIP(c, rt::launch_present_scaled(c->d_image, c->cfg.width, c->cfg.height, dst, out_width, out_height,
-                                      top_down != 0, st));
+                                      top_down != 0, st, c->log));
   c->d_scaled = dst;
   c->scaled_w = out_width;
   c->scaled_h = out_height;
@@ -1295,7 +1325,7 @@ int rt_trace_rays_device(rt_ctx* c, const void* d_origins, const void* d_dirs, s
   q.t = (float*)d_t;
   q.ind = (int*)d_ind;
   q.nrm = (float*)d_normals;
-  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv)));
+  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv), c->log));
   return RT_OK;
 }
 
@@ -1313,7 +1343,7 @@ int rt_trace_pixels_device(rt_ctx* c, const void* d_xy, size_t n, float thr, voi
   q.ind = (int*)d_ind;
   q.nrm = (float*)d_normals;
   q.dir_out = (float*)d_dirs;
-  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv)));
+  RT_HIP(c, rt::launch_ray_query(q, c->stream, query_tree(c, tv), c->log));
   return RT_OK;
 }
 
@@ -1322,7 +1352,7 @@ int rt_occluded_device(rt_ctx* c, const void* d_from, const void* d_to, size_t n
   rt::QueryTree tv{};
   if (!d_out) return RT_OK;
   RT_HIP(c, rt::launch_occluded(query_scene(c), (const float*)d_from, (const float*)d_to, n, (unsigned char*)d_out,
-                                c->stream, query_tree(c, tv)));
+                                c->stream, query_tree(c, tv), c->log));
   return RT_OK;
 }
 
@@ -1477,7 +1507,7 @@ int rt_selftest_math(rt_ctx* c, int fn, const float* in, float* out, size_t n) {
   RT_HIP(c, hipMalloc(&din, std::max<size_t>(ib, 4)));
   hipError_t e = hipMalloc(&dout, std::max<size_t>(ob, 4));
   if (e == hipSuccess) e = hipMemcpy(din, in, ib, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = rt::launch_selftest(fn, din, dout, n, c->stream);
+  if (e == hipSuccess) e = rt::launch_selftest(fn, din, dout, n, c->stream, c->log);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
   (void)hipFree(din);

@@ -373,6 +373,21 @@ class Renderer:
         """Test hook (rt_debug_cull_cache_cap): this context's cap on the cull cache, before its first fill."""
         self._c(self._lib.rt_debug_cull_cache_cap(self.ctx, int(nbytes)), "rt_debug_cull_cache_cap")
 
+    def set_launch_log(self, on: bool):
+        """Test hook (rt_debug_launch_log): record the form of every kernel this context launches; off empties the log."""
+        self._c(self._lib.rt_debug_launch_log(self.ctx, int(bool(on))), "rt_debug_launch_log")
+
+    def launch_log(self, reset: bool = False) -> list:
+        """The forms launched since the log was switched on or last reset, in launch order
+        (rt_debug_launch_log_read), e.g. "ao_batch_kernel<AoProd<16, 20, 70u>>"."""
+        need = self._lib.rt_debug_launch_log_read(self.ctx, None, 0, 0)
+        if need < 0:
+            self._c(int(need), "rt_debug_launch_log_read")
+        buf = C.create_string_buffer(int(need))
+        self._c(min(0, int(self._lib.rt_debug_launch_log_read(self.ctx, buf, int(need), int(bool(reset))))),
+                "rt_debug_launch_log_read")
+        return buf.value.decode().splitlines()
+
     def download(self, pixels=True, normals=True, depth=True, image=True) -> GBuffer:
         shp = (self.F, self.W, self.R, 4)
         p = np.empty(shp, np.float32) if pixels else None
@@ -842,6 +857,17 @@ def query_tree_host(header: Header, rectangles: bool = False) -> dict:
         raise ValueError("rt_query_tree_host rejected the header")
     return {"balls": balls[:n].copy(), "links": links[:n].copy(), "leaf_rows": rows[:e.value].copy(),
             "leaf_index": index[:e.value].copy(), "always": always[:a.value].copy()}
+
+
+def ao_form_host(spp: int, depth: int, ncl: int, nobj: int, nplanes: int = 0, nrects: int = 0, counters: bool = False,
+                 multi_frame: bool = False, cull_table: bool = False) -> str:
+    """rt_ao_form_host (host only): the form the AO launcher's selector picks for such a launch, by
+    the name the launch log gives it ("ao_batch_kernel<AoProd<sppc, dc, flagsu>>")."""
+    out = (C.c_int * 3)()
+    _check(_lib.load().rt_ao_form_host(int(spp), int(depth), int(ncl), int(nobj), int(nplanes), int(nrects),
+                                       int(bool(counters)), int(bool(multi_frame)), int(bool(cull_table)), out),
+           "rt_ao_form_host")
+    return f"ao_batch_kernel<AoProd<{out[0]}, {out[1]}, {out[2]}u>>"
 
 
 def plan_strips(row_cost, n: int) -> list[int]:

@@ -271,14 +271,15 @@ static bool ab_general() {
   return eg && atoi(eg) == 1;
 }
 
-hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream) {
+// (log: the production launches record their forms; the A/B variants selected here record nothing)
+hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream, LaunchLog* log) {
   if (p.trace_rows <= 0) return hipSuccess;
   if (const char* es = getenv("RTRT_POST_SKIP"); es && atoi(es) == 1 && program == K_POST) return hipSuccess;  // A/B floor
   FrameParams q = launch_params(p);
   const bool pl = p.nplanes > 0;
   if (program == K_AOP || program == K_AO) {
     if (ab_launch_ao(p, q, stream, (long long)p.trace_rows * p.W)) return hipGetLastError();
-    return launch_production(program, p, q, stream);
+    return launch_production(program, p, q, stream, log);
   }
   const int fpb = program == K_PHONG ? kPhongFramesPerBlock : kHybridFramesPerBlock;
   dim3 grid((p.W + 15) / 16, (p.trace_rows + 15) / 16, p.mf_n > 0 ? (p.mf_n + fpb - 1) / fpb : 1);
@@ -324,7 +325,7 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream)
     else hipLaunchKernelGGL((hybrid_kernel<false>), grid, dim3(kBlock), lds, stream, q.tile_order, q.sph, q.shapes, grid.x, q);
     return hipGetLastError();
   }
-  return launch_production(program, p, q, stream);
+  return launch_production(program, p, q, stream, log);
 }
 
 }  // namespace rt
