@@ -11,8 +11,13 @@
 //   rt_headless [--width W] [--height H] [--objects N] [--spp A] [--mode 1..4] [--frames K]
 //               [--scene synthetic|1|5|6|7] [--rectangles 0|1] [--seed S] [--device D] [--ppm out.ppm] [--pipeline 0|1]
 //               [--strips G] [--devices d0,d1,...] [--balance ROUNDS] [--ppm-size WxH] [--pick X,Y] [--query-tree 0|1]
+//               [--mesh FILE.obj]
 // --pick X,Y prints, after the last frame, one line `pick x y ind t nx ny nz`: the closest hit of pixel
 // (X, Y)'s primary ray (frame coordinates, row 0 = the bottom row) by rt_trace_pixels at threshold 0.
+// --mesh FILE.obj loads a triangle mesh (include/rt/mesh.h, librtrt_mesh.so; the frames do not show it) and
+// makes --pick answer for scene and mesh together: rt_trace_pixels, then rt_mesh_trace_rays on the pixel's ray
+// from the camera with RT_MESH_MERGE.  The line is then `pick x y ind t nx ny nz prim`: prim the mesh's
+// triangle where the mesh is strictly closer (ind is then -1), else -1.
 // --rectangles 1 turns rt_set_rectangles on (rt_group_set_rectangles with --strips): rectangles are drawn,
 // e.g. the area light of --scene 7 (scene 5 with the rectangle light the reference left commented out).
 // --strips G > 1 renders the frame as G row strips through the rt_group_* entry points: strip i
@@ -28,6 +33,7 @@
 #include <vector>
 
 #include "rt/abi.h"
+#include "rt/mesh.h"
 
 static int check(int rc, const char* what) {
   if (rc < 0) {
@@ -116,12 +122,26 @@ static int run_strips(const rt_config& cfg, std::vector<float>& header, int mode
   return 0;
 }
 
+// the file's bytes; exits with a message if it cannot be read
+static std::string read_file(const std::string& path) {
+  std::string text;
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) {
+    std::fprintf(stderr, "rt_headless: cannot open %s\n", path.c_str());
+    std::exit(1);
+  }
+  char buf[65536];
+  for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+  std::fclose(f);
+  return text;
+}
+
 int main(int argc, char** argv) {
   int W = 440, H = 330, N = 5, A = 4, mode = 1, frames = 8, device = 0, pipeline = 0, strips = 1, balance = 0, rectangles = 0, query_tree = 0;
   int ppm_w = 0, ppm_h = 0;  // --ppm-size (0: the frame's own size)
   bool pick = false;         // --pick X,Y: what is under that pixel after the last frame
   int pick_x = 0, pick_y = 0;
-  std::string scene = "1", ppm, devlist;
+  std::string scene = "1", ppm, devlist, mesh_path;
   unsigned long long seed = 1234;
   for (int i = 1; i + 1 < argc; i += 2) {
     std::string k = argv[i], v = argv[i + 1];
@@ -140,6 +160,7 @@ int main(int argc, char** argv) {
     else if (k == "--query-tree") query_tree = std::atoi(v.c_str());  // --pick through the query tree (rt_set_query_tree)
     else if (k == "--strips") strips = std::atoi(v.c_str());
     else if (k == "--devices") devlist = v;
+    else if (k == "--mesh") mesh_path = v;
     else if (k == "--balance") balance = std::atoi(v.c_str());
     else if (k == "--ppm-size") {
       if (std::sscanf(v.c_str(), "%dx%d", &ppm_w, &ppm_h) != 2 || ppm_w < 1 || ppm_h < 1 ||
@@ -157,6 +178,10 @@ int main(int argc, char** argv) {
     }
     else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
+  if (!mesh_path.empty() && strips > 1) {
+    std::fprintf(stderr, "rt_headless: --mesh goes with --pick on one context; it does not go with --strips\n");
+    return 2;
+  }
   if (pick && strips > 1) {
     std::fprintf(stderr, "rt_headless: --pick asks one context; it does not go with --strips\n");
     return 2;
@@ -170,8 +195,26 @@ int main(int argc, char** argv) {
   rt_config cfg{W, H, S, A, RT_NUM_FRAMES, RT_RECURSION_DEPTH, 0, 0};
   if (strips > 1) return run_strips(cfg, header, mode, frames, pipeline, rectangles, strips, devlist, device, balance, ppm,
                                 ppm_w, ppm_h);
+  // the mesh's geometry is read (and a malformed file refused) before anything touches the GPU
+  std::vector<float> mesh_verts;
+  std::vector<int32_t> mesh_tris;
+  if (!mesh_path.empty()) {
+    const std::string text = read_file(mesh_path);
+    int nv = 0, nt = 0, bad_line = 0;
+    if (rt_obj_parse(text.data(), text.size(), nullptr, 0, nullptr, 0, &nv, &nt, &bad_line) != RT_OK) {
+      std::fprintf(stderr, "rt_headless: %s: line %d is malformed\n", mesh_path.c_str(), bad_line);
+      return 1;
+    }
+    mesh_verts.resize(3 * (size_t)nv);
+    mesh_tris.resize(3 * (size_t)nt);
+    check(rt_obj_parse(text.data(), text.size(), mesh_verts.data(), nv, mesh_tris.data(), nt, &nv, &nt, &bad_line), "rt_obj_parse");
+  }
   rt_ctx* ctx = nullptr;
   check(rt_create(device, &cfg, &ctx), "rt_create");
+  rt_mesh* mesh = nullptr;
+  if (!mesh_path.empty())
+    check(rt_mesh_create(device, mesh_verts.data(), (int)(mesh_verts.size() / 3), mesh_tris.data(), (int)(mesh_tris.size() / 3), &mesh),
+          "rt_mesh_create");
   check(rt_enable_timing(ctx, 1), "rt_enable_timing");
   if (pipeline) check(rt_enable_pipelining(ctx, 1, nullptr), "rt_enable_pipelining");
   if (rectangles) check(rt_set_rectangles(ctx, 1), "rt_set_rectangles");
@@ -213,9 +256,19 @@ int main(int argc, char** argv) {
     const int32_t xy[2] = {pick_x, pick_y};
     float t = 0.0f, nrm[3] = {0.0f, 0.0f, 0.0f};
     int32_t ind = 0;
-    check(rt_trace_pixels(ctx, xy, 1, 0.0f, &t, &ind, nrm, nullptr), "rt_trace_pixels");
-    std::printf("pick %d %d %d %.9g %.9g %.9g %.9g\n", pick_x, pick_y, (int)ind, t, nrm[0], nrm[1], nrm[2]);
+    float dir[3] = {0.0f, 0.0f, 0.0f};
+    check(rt_trace_pixels(ctx, xy, 1, 0.0f, &t, &ind, nrm, mesh ? dir : nullptr), "rt_trace_pixels");
+    if (mesh) {  // the same ray on the mesh, merged: the mesh takes the pixel only where it is strictly closer
+      int32_t prim = -1;
+      check(rt_mesh_trace_rays(mesh, &header[4 * RT_HDR_CAMERA_LOCATION], dir, 1, RT_MESH_ONE_ORIGIN | RT_MESH_MERGE, 0.0f, &t,
+                               &prim, nrm, nullptr), "rt_mesh_trace_rays");
+      if (prim >= 0) ind = -1;
+      std::printf("pick %d %d %d %.9g %.9g %.9g %.9g %d\n", pick_x, pick_y, (int)ind, t, nrm[0], nrm[1], nrm[2], (int)prim);
+    } else {
+      std::printf("pick %d %d %d %.9g %.9g %.9g %.9g\n", pick_x, pick_y, (int)ind, t, nrm[0], nrm[1], nrm[2]);
+    }
   }
+  if (mesh) rt_mesh_destroy(mesh);
   rt_destroy(ctx);
   return 0;
 }
