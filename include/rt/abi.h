@@ -203,6 +203,33 @@ size_t rt_cull_cache_frame_bytes(rt_ctx* ctx);
 /* Test hook: this context's cap on the cull cache's bytes, in place of the build's 512 MiB
  * (0 restores it).  Before the first fill only. */
 int rt_debug_cull_cache_cap(rt_ctx* ctx, size_t bytes);
+/* Pool list of the cull cache, on by default.  Which pools of an AO launch are sky (no sphere in
+ * their masks), and every other pool's first pixel and pixel count, depend on the cache's key alone.
+ * A fill that keeps frames therefore also writes, in front of them in the same allocation (16 bytes
+ * per pool, a word per 4096 pools and 16 bytes more; counted against the same cap, and left out,
+ * with masks and frames kept, when the three do not fit), the non-sky pools' rows (pool, x, y,
+ * pixels) and the sky pools' indices, both in ascending pool order, the same bytes for the same
+ * key.  It is written by two further launches of the fill's kernel, which the launch log counts
+ * with the fill's one entry.  The two counts come back to pinned host memory behind an event that
+ * the launches poll and never wait for: until it has fired they run as before; from then on the
+ * single-frame launches of the sorted, cached forms without counters run one workgroup per non-sky
+ * pool, which reads its row in place of the pool start's divisions, and one per 64 sky pools.
+ * Every other form launches as before, and so does a camera that moves every frame.  Images and
+ * g-buffers are bit-identical either way.  The list follows the masks in everything else: key,
+ * invalidation, streams, strips.  on = 0: no list is written or used (the key has to hold anew). */
+int rt_set_pool_list(rt_ctx* ctx, int on);
+/* List builds and launches over a list since rt_create, the current list's counts (-1 while there
+ * is none, or its counts have not landed) and the list's bytes in the allocation (0: none).  The
+ * allocation is made once, at the context's first fill, and has the list's room whenever it fits the
+ * cap, also while the switch is off (the bytes are then reserved and never written), so that
+ * switching the list on later needs no second allocation.  Any pointer may be NULL. */
+int rt_pool_list_stats(rt_ctx* ctx, long long* builds, long long* list_launches, int* n_nonsky, int* n_sky,
+                       size_t* bytes);
+/* Test hook: after waiting for the device, copy to buf what the cache holds for the current key:
+ * what = 0 the list's rows (16 bytes each), 1 the sky pools' indices (4 bytes each, as stored: the
+ * last entry first), 2 the masks.  Returns the bytes needed (copied when they fit in cap), or a
+ * negative status: RT_E_STATE without a filled table (what = 0, 1: without a list). */
+long long rt_debug_pool_list_read(rt_ctx* ctx, int what, void* buf, size_t cap);
 /* Launch log (test hook, off by default).  While on, the context records the form of every kernel
  * it launches, in launch order, at the point where its launcher picks the kernel: the render
  * programs, the cull cache's fill, the ray queries, the 8-bit presents, the g-buffer layout
@@ -548,6 +575,8 @@ int rt_group_set_phong_gbuffer(rt_group* g, int on);
 int rt_group_set_rectangles(rt_group* g, int on);
 /* rt_set_query_tree on every strip; kept in the same way. */
 int rt_group_set_query_tree(rt_group* g, int on);
+/* rt_set_pool_list on every strip; kept in the same way. */
+int rt_group_set_pool_list(rt_group* g, int on);
 /* Assemble frames into a caller-owned device buffer of H*W float4 on devices[0] (NULL: the
  * group's own).  Waits for the frames in flight first. */
 int rt_group_bind_frame(rt_group* g, void* device_ptr);

@@ -78,6 +78,10 @@ SIGNATURES = {
     "rt_cull_cache_stats": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]),
     "rt_cull_cache_frame_bytes": (C.c_size_t, [_ctx]),
     "rt_debug_cull_cache_cap": (C.c_int, [_ctx, C.c_size_t]),
+    "rt_set_pool_list": (C.c_int, [_ctx, C.c_int]),
+    "rt_pool_list_stats": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "rt_debug_pool_list_read": (C.c_longlong, [_ctx, C.c_int, _vp, C.c_size_t]),
     "rt_debug_launch_log": (C.c_int, [_ctx, C.c_int]),
     "rt_debug_launch_log_read": (C.c_longlong, [_ctx, C.c_char_p, C.c_size_t, C.c_int]),
     "rt_ao_form_host": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
@@ -134,6 +138,7 @@ SIGNATURES = {
     "rt_group_set_phong_gbuffer": (C.c_int, [_grp, C.c_int]),
     "rt_group_set_rectangles": (C.c_int, [_grp, C.c_int]),
     "rt_group_set_query_tree": (C.c_int, [_grp, C.c_int]),
+    "rt_group_set_pool_list": (C.c_int, [_grp, C.c_int]),
     "rt_group_bind_frame": (C.c_int, [_grp, _vp]),
     "rt_group_frame_device_ptr": (_vp, [_grp]),
     "rt_group_upload_header": (C.c_int, [_grp, _vp, C.c_size_t]),

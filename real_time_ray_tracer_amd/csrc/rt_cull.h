@@ -55,6 +55,21 @@ struct CullCache {
   int n_read = 0;                    // ev_read[0 .. n_read) are recorded and not yet waited for
   long long fills = 0, cached = 0;   // rt_cull_cache_stats
   LaunchLog* log = nullptr;          // the context's launch log while it is on (rt_debug_launch_log)
+  // Pool list (rt_kernels.h ao_pool_list_bytes): the non-sky pools' (pb, xf, yf, np) rows and the
+  // sky pools' indices, in front of the frames in the same allocation when masks, frames and list
+  // fit the cap together.  Written on the fill's stream right after the fill; its two counts are
+  // copied to pinned memory behind it and ev_list recorded.  The launches poll that event and never
+  // wait for it: until it has fired they run the cached kernel over every pool, from then on over
+  // the list's blocks (FrameParams::cull_frames == 2).  Key, allocation, ev_fill / ev_read and
+  // invalidation are the masks'.
+  bool list_on = true;               // rt_set_pool_list
+  size_t list_bytes = 0;             // 0: no list in this allocation
+  long long list_pools = 0;          // the pools the list was laid out for
+  int* h_counts = nullptr;           // pinned: (n_nonsky, n_sky, 0, 0)
+  hipEvent_t ev_list = nullptr;
+  bool list_pending = false;         // written for the current fill; ev_list has not been seen fired
+  bool list_ready = false;           // h_counts holds the current fill's counts
+  long long list_builds = 0, list_launches = 0;  // rt_pool_list_stats
 
   // Before an AO launch of p (its rows, tables and camera set) on st, of a context with
   // configuration cfg and header h: compare its key with the previous launch's and hand it the

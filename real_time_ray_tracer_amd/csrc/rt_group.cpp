@@ -117,6 +117,7 @@ struct rt_group {
   bool phong_gbuf = false;  // rt_group_set_phong_gbuffer: kept across re-created strips, as pipelining is
   bool rectangles = false;  // rt_group_set_rectangles: kept in the same way
   bool query_tree = false;  // rt_group_set_query_tree: kept in the same way
+  bool pool_list = true;    // rt_group_set_pool_list: kept in the same way
   std::vector<rt_ctx*> ctx;
   float4* frame_own = nullptr;  // [H][W] on devices[0]
   float4* frame = nullptr;      // the bound frame (own or the caller's)
@@ -192,6 +193,7 @@ int make_strips(rt_group* g) {
     if (rc == RT_OK && g->phong_gbuf) rc = rt_set_phong_gbuffer(g->ctx[i], 1);
     if (rc == RT_OK && g->rectangles) rc = rt_set_rectangles(g->ctx[i], 1);
     if (rc == RT_OK && g->query_tree) rc = rt_set_query_tree(g->ctx[i], 1);
+    if (rc == RT_OK && !g->pool_list) rc = rt_set_pool_list(g->ctx[i], 0);
     if (rc != RT_OK) {
       destroy_strips(g);
       return rc;
@@ -640,6 +642,16 @@ int rt_group_set_query_tree(rt_group* g, int on) {
   g->query_tree = on != 0;
   for (auto* c : g->ctx) {
     int rc = rt_set_query_tree(c, on);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+int rt_group_set_pool_list(rt_group* g, int on) {
+  if (!g) return RT_E_INVAL;
+  g->pool_list = on != 0;
+  for (auto* c : g->ctx) {
+    int rc = rt_set_pool_list(c, on);
     if (rc != RT_OK) return rc;
   }
   return RT_OK;

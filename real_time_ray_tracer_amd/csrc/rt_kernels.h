@@ -41,7 +41,8 @@ struct FrameParams {
   int S;                     // stride of the compact shape table (capacity)
   int spp, D, F, frame;
   int b1_min;                // AO: least live lanes of a prepared batch for its batched first bounce (set at launch)
-  int pool_rot;              // AO: pools per rotation group (one row's; 0 = pools in row order; set at launch)
+  int pool_rot;              // AO: pools per rotation group (one row's; 0 = pools in row order; set at launch); a pool-list
+                             // launch (cull_frames == 2) has no rotation: the list's non-sky pools, set by the cull cache
   int tile_run;              // post-process: tiles per XCD run (xcd_tile; set at launch)
   int post_sx, post_sy;      // post-process: super-tiles of post_sx x post_sy blocks per XCD visit (xcd_tile)
   float inv_spp, fW, fH;     // 1.0f / spp, (float)W, (float)H: host-computed wave-uniform constants
@@ -108,6 +109,11 @@ struct FrameParams {
   // (const float4*)cull - 2 (pb + 1): (e1, 0), (e2, 0), two unit vectors orthogonal to the surface
   // normal at the hit of the pool's unjittered centre ray (launch_cull_fill); the sorted kernels
   // then deal the pool's samples by the sector of their bounce hemisphere point around that normal
+  // cull_frames == 2 (single-frame launches of those kernels only, ao_takes_pool_list): in front of
+  // the frames the allocation holds the pool list as well (ao_pool_list_bytes), and the grid is
+  // ao_pool_list_blocks(pool_rot, pools - pool_rot): block b < pool_rot renders the pool of the
+  // list's row b, read with one scalar load in place of the pool start's index arithmetic, and
+  // each later block stores 64 of the list's sky pools
   const unsigned long long* cull;
 };
 static_assert(offsetof(FrameParams, bg) == 160 && offsetof(FrameParams, cull_frames) == 156,
@@ -119,6 +125,24 @@ static_assert(offsetof(FrameParams, ncl) == 232 && offsetof(FrameParams, nrects)
 
 // bytes of the sort frames in front of a cull table of `pools` pools (two float4 per pool)
 constexpr size_t ao_cull_frame_bytes(long long pools) { return (size_t)pools * 2 * sizeof(float4); }
+
+// The pool list, in front of the sort frames in the same allocation (launch_pool_list writes it from
+// the masks; FrameParams::cull_frames == 2 selects it).  From its first byte:
+//   16 x pools bytes  the non-sky pools' rows upwards from the start, int4 (pb, xf, yf, np) in
+//                     ascending pb: a pool with a sphere in its masks, the first pixel's column and
+//                     frame row and the pool's pixel count as ao_batch_kernel's pool start forms
+//                     them; the sky pools' pb, 4 bytes each, downwards from the end (entry j at
+//                     ((unsigned*)end)[-1 - j], ascending too): 16 n_nonsky + 4 n_sky <= 16 pools
+//   chunk counts      one unsigned per kPoolListChunk pools, the non-sky pools of the chunk (the
+//                     build's scratch), padded to 16 bytes
+//   16 bytes          (n_nonsky, n_sky, 0, 0)
+constexpr int kPoolListChunk = 4096;
+constexpr size_t ao_pool_list_chunk_bytes(long long pools) {
+  return (((size_t)(pools + kPoolListChunk - 1) / kPoolListChunk) * sizeof(unsigned) + 15) & ~(size_t)15;
+}
+constexpr size_t ao_pool_list_bytes(long long pools) { return (size_t)pools * 16 + ao_pool_list_chunk_bytes(pools) + 16; }
+// blocks of a pool-list launch: one per non-sky pool, then one per 64 sky pools
+constexpr long long ao_pool_list_blocks(long long n_nonsky, long long n_sky) { return n_nonsky + (n_sky + 63) / 64; }
 
 enum KernelId { K_AOP = 1, K_POST = 2, K_AO = 3, K_PHONG = 4, K_HYBRID = 5 };
 
@@ -149,6 +173,16 @@ hipError_t launch_program(int program, const FrameParams& p, hipStream_t stream,
 // reaches a result, it only orders a pool's samples.
 hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, bool frames, hipStream_t stream,
                             LaunchLog* log = nullptr);
+// Write the pool list (ao_pool_list_bytes) in front of the frames of `table`, which launch_cull_fill
+// filled with frames on the same stream: two further launches of its kernel, selected by
+// FrameParams::cull_frames as a mode word, one block per kPoolListChunk pools.  The first counts each
+// chunk's non-sky pools; in the second every block sums the counts of the chunks before its own and
+// writes its chunk's rows and sky entries in pool order, so a list is the same bytes from build to
+// build.  Part of the fill: the launch log has the fill's one entry.
+hipError_t launch_pool_list(const FrameParams& p, unsigned long long* table, hipStream_t stream);
+// Whether an AO launch of p handed a cull table with frames may be handed the pool list as well: the
+// single-frame sorted, cached forms without counters, and a pixel count a 32-bit index holds.
+bool ao_takes_pool_list(const FrameParams& p);
 
 // g-buffer layout conversion between the reference's [F][W][R] vec4 (x-major, y fastest:
 // src/main.cpp:49-85 over a context's R rows) and the device slots of one array kind (0 pixels:

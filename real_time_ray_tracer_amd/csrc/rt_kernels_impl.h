@@ -1297,6 +1297,46 @@ constexpr bool sector_code_ok() {
 }
 static_assert(sector_code_ok(), "sector_code: the 8 sectors in circular order");
 
+// The pool list in front of a cull table's sort frames (rt_kernels.h ao_pool_list_bytes), addressed
+// from the mask table's pointer as the frames are: the rows upwards from the list's first byte, the
+// sky list downwards from the rows' end, where the chunk counts start.
+__device__ __forceinline__ const int4* pool_list_rows(const void* table, unsigned pools) {
+  return (const int4*)((const char*)table - ao_cull_frame_bytes(pools) - ao_pool_list_bytes(pools));
+}
+__device__ __forceinline__ const unsigned* pool_list_sky_end(const void* table, unsigned pools) {
+  return (const unsigned*)(pool_list_rows(table, pools) + pools);
+}
+
+// A sky block of a pool-list launch (FrameParams::cull_frames == 2): sky pools [first, first + 64)
+// of the list, one pixel per lane and step.  What the pool's own sky exit stores (below), pixel for
+// pixel: the same float sequence for the colour, through the same stores.  No LDS, no barrier.
+// npix < 2^31 (the cull cache builds no list above), so a pixel's index is a 32-bit number.
+template <int SPPC>
+__device__ __forceinline__ void ao_sky_block(const FrameParams& P, const unsigned* __restrict__ sky_end, unsigned first,
+                                             unsigned nsky, unsigned npix) {
+  const int spp = SPPC ? SPPC : P.spp;
+  const unsigned TP = kPool / spp > 0 ? kPool / spp : 1, W = (unsigned)P.W;
+  const float fa = (float)spp;
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f;
+  for (int k = 0; k < spp; ++k) {
+    sr = sr + 1.0f * P.bg.x; sg = sg + 1.0f * P.bg.y; sb = sb + 1.0f * P.bg.z;
+  }
+  const float4 col = gamma_out(sr / fa, sg / fa, sb / fa);
+  const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  for (unsigned e = threadIdx.x; e < 64u * TP; e += 64) {
+    const unsigned q = e / TP, j = first + q;
+    if (j >= nsky) break;  // (j grows with e: the lanes past the list's end are done)
+    const unsigned pix = sky_end[-1 - (long long)j] * TP + (e - q * TP);
+    if (pix >= npix) continue;  // the frame's last pool may be partial
+    const unsigned yr = pix / W;
+    const int x = (int)(pix - yr * W), y = P.trace_row0 + (int)yr;
+    const size_t off = (size_t)(y - P.band_row0) * W + x;
+    nrm_store(P.nrm, dep_plane(P), off, z);
+    dep_store(P.dep, dep_plane(P), off, z);
+    store_color(P, P.out_pix, P.image, x, y, col);
+  }
+}
+
 // geo: the sphere table (P.sph).  The bounce-ray cluster cull of the later bounce rounds runs
 // whenever the launch has clusters (P.ncl > 0); without them the rounds test every sphere.
 // cullt: the pools' cull masks (P.cull), read by CULLC only; an argument of its own, read-only and
@@ -1333,6 +1373,23 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
   const int TP = kPool / spp > 0 ? kPool / spp : 1;
   const int lane = threadIdx.x;
   const int NS = TP * spp;
+  // A pool-list launch (FrameParams::cull_frames == 2; the single-frame forms that take frames):
+  // the blocks behind the non-sky pools' store the list's sky pools, before any LDS is touched.
+  constexpr bool LIST = NSORT && !MF;
+  bool listed = false;  // wave-uniform
+  unsigned list_pools = 0;
+  if constexpr (LIST) {
+    listed = P.cull_frames == 2;
+    if (listed) {
+      const unsigned npx = (unsigned)P.trace_rows * (unsigned)W, nns = (unsigned)P.pool_rot;
+      list_pools = (npx + (unsigned)TP - 1) / (unsigned)TP;
+      if (blockIdx.x >= nns) {
+        __builtin_amdgcn_s_setprio(0);
+        ao_sky_block<SPPC>(P, pool_list_sky_end(cullt, list_pools), (blockIdx.x - nns) * 64, list_pools - nns, npx);
+        return;
+      }
+    }
+  }
   // PTW (scenes above kTailMaxObj spheres): the first bounce's pre-test rows one 64-sphere word at a
   // time in LDS, the split tail rounds on the global table, and rand_buffer read from global memory
   // (its LDS copy would not leave room for the rows at 7 waves per SIMD with spp 64)
@@ -1392,7 +1449,13 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
   // rotating row r's pools by r (groups of pool_rot = pools per row) moves each XCD's columns by
   // one pool per row, so over 8 rows every XCD samples every column residue (a bijection on the
   // full groups; the last, partial group keeps its order).  Config (d) AO launch: -3%.
-  if (P.pool_rot > 0) {
+  // A pool-list launch reads pb and the pool's (xf, yf, np) below from the block's row instead (one
+  // scalar load: a wave-uniform address); the rotation and the divisions are not executed.
+  int4 row = make_int4(0, 0, 0, 0);
+  if (LIST && listed) {
+    row = pool_list_rows(cullt, list_pools)[blockIdx.x];
+    pb = (unsigned)row.x;
+  } else if (P.pool_rot > 0) {
     const unsigned Q = (unsigned)P.pool_rot, r = pb / Q;
     if ((r + 1) * Q <= gridDim.x) {
       unsigned c = pb - r * Q + r % Q;
@@ -1400,8 +1463,8 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
       pb = r * Q + c;
     }
   }
-  const long long p0 = (long long)pb * TP;
-  const int np = (int)(npix - p0 < TP ? npix - p0 : TP);
+  const long long p0 = (long long)pb * TP;  // (not read by a pool-list launch)
+  const int np = LIST && listed ? row.w : (int)(npix - p0 < TP ? npix - p0 : TP);
   const int total = np * spp;
 
   // ABL == 3: per-section wave clock (s_memtime) into the counters, timing ablation only
@@ -1420,7 +1483,8 @@ __global__ __launch_bounds__(64, kAoMinWaves) void ao_batch_kernel(FrameParams P
     }
   };
   // ---- frustum cull of the primary rays -------------------------------------------------
-  const int yf = P.trace_row0 + (int)(p0 / W), xf = (int)(p0 % W);  // once per pool (scalar)
+  // once per pool (scalar)
+  const int yf = LIST && listed ? row.z : P.trace_row0 + (int)(p0 / W), xf = LIST && listed ? row.y : (int)(p0 % W);
   // pixel lp of the pool: (xf + lp, yf), wrapped into the next row(s) when it passes W
   auto pool_xy = [&](int lp, int& x, int& y) {
     int xi = xf + lp;
@@ -2711,9 +2775,65 @@ size_t tab_lds_bytes(const FrameParams& p) { return (size_t)5 * (p.nobj > 0 ? p.
 // pool); e1 = normalize(n0 x ref), e2 = n0 x e1, ref the x axis unless |n0.x| >= 0.9, then the y
 // axis.  Raw v_rsq: the frame orders the pool's samples and nothing else.  Every lane computes the
 // same values (one uniform ray), lane 0 stores them.
+//
+// The pool list (rt_kernels.h ao_pool_list_bytes) is written from the filled masks by two further
+// launches of the FRAMES kernel with P.cull_frames as a mode word (launch_pool_list), block c over
+// chunk c of kPoolListChunk pools, 64 pools a step, one per lane.  A pool is sky when its masks are
+// all zero, the ncull == 0 of ao_batch_kernel's sky exit.  Mode 1: the chunk's non-sky count.  Mode
+// 2: the block sums the counts of the chunks before its own, then a pool's row index is that sum
+// plus the non-sky pools before it in the chunk (ballots), and its sky index the pools before it
+// less those: both lists ascend in pb whatever order the blocks run in.  The last block writes
+// the two counts.  (xf, yf, np): ao_batch_kernel's pool start, expression for expression.
+__device__ __forceinline__ void pool_list_build(const FrameParams& P, unsigned long long* table, bool write) {
+  const int spp = P.spp, W = P.W;
+  const int TP = kPool / spp > 0 ? kPool / spp : 1;
+  const unsigned lane = threadIdx.x, chunk = blockIdx.x;
+  const long long npix = (long long)P.trace_rows * W;
+  const unsigned pools = (unsigned)((npix + TP - 1) / TP), nwords = (unsigned)(P.nobj + 63) >> 6;
+  char* const base = (char*)table - ao_cull_frame_bytes(pools) - ao_pool_list_bytes(pools);
+  int4* const rows = (int4*)base;
+  unsigned* const sky_end = (unsigned*)(base + 16 * (size_t)pools);
+  unsigned* const counts = sky_end;  // the chunk counts start where the rows' 16 x pools bytes end
+  unsigned before = 0;  // non-sky pools in front of the step's 64
+  if (write) {
+    for (unsigned k = lane; k < chunk; k += 64) before += counts[k];
+    before = wave_sum(before);
+  }
+  const unsigned first = chunk * (unsigned)kPoolListChunk;
+  for (unsigned s = 0; s < (unsigned)kPoolListChunk && first + s < pools; s += 64) {
+    const unsigned pb = first + s + lane;
+    bool nonsky = false;
+    if (pb < pools)
+      for (unsigned w = 0; w < nwords; ++w) nonsky = nonsky || table[(size_t)pb * nwords + w] != 0;
+    const unsigned long long m = __ballot(nonsky);
+    if (write && pb < pools) {
+      const unsigned at = before + (unsigned)__popcll(m & ((1ull << lane) - 1));
+      if (nonsky) {
+        const long long p0 = (long long)pb * TP;
+        const int np = (int)(npix - p0 < TP ? npix - p0 : TP);
+        const int yf = P.trace_row0 + (int)(p0 / W), xf = (int)(p0 % W);
+        rows[at] = make_int4((int)pb, xf, yf, np);
+      } else {
+        sky_end[-1 - (long long)(pb - at)] = pb;
+      }
+    }
+    before += (unsigned)__popcll(m);
+  }
+  if (lane != 0) return;
+  if (!write) counts[chunk] = before;
+  else if (chunk == gridDim.x - 1)
+    *(int4*)((char*)table - ao_cull_frame_bytes(pools) - 16) = make_int4((int)before, (int)(pools - before), 0, 0);
+}
+
 template <bool FRAMES>
 __global__ __launch_bounds__(64) void cull_fill_kernel(FrameParams P, const float4* __restrict__ geo,
                                                        unsigned long long* __restrict__ table) {
+  if constexpr (FRAMES) {
+    if (P.cull_frames != 0) {  // (wave-uniform) the pool list's build, not the fill
+      pool_list_build(P, table, P.cull_frames == 2);
+      return;
+    }
+  }
   const int spp = P.spp, W = P.W, nobj = P.nobj;
   const int TP = kPool / spp > 0 ? kPool / spp : 1;
   const int lane = threadIdx.x;
@@ -2796,8 +2916,22 @@ hipError_t launch_cull_fill(const FrameParams& p, unsigned long long* table, boo
   const long long pools = ao_pool_count(p.trace_rows, p.W, p.spp);
   if (pools <= 0 || p.nobj <= 0) return hipSuccess;
   const float4* const sph = p.shapes + sphere_table(p.S);
-  if (frames) RT_LAUNCH(log, "cull_fill_kernel<true>", cull_fill_kernel<true>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
-  else RT_LAUNCH(log, "cull_fill_kernel<false>", cull_fill_kernel<false>, dim3((unsigned)pools), dim3(64), 0, stream, p, sph, table);
+  FrameParams q = p;
+  q.cull_frames = 0;  // (the FRAMES kernel's mode word: the fill)
+  if (frames) RT_LAUNCH(log, "cull_fill_kernel<true>", cull_fill_kernel<true>, dim3((unsigned)pools), dim3(64), 0, stream, q, sph, table);
+  else RT_LAUNCH(log, "cull_fill_kernel<false>", cull_fill_kernel<false>, dim3((unsigned)pools), dim3(64), 0, stream, q, sph, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_list(const FrameParams& p, unsigned long long* table, hipStream_t stream) {
+  const long long pools = ao_pool_count(p.trace_rows, p.W, p.spp);
+  if (pools <= 0 || p.nobj <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((pools + kPoolListChunk - 1) / kPoolListChunk));
+  FrameParams q = p;
+  for (int mode = 1; mode <= 2; ++mode) {  // (not logged: part of the fill, whose entry launch_cull_fill made)
+    q.cull_frames = mode;
+    hipLaunchKernelGGL(cull_fill_kernel<true>, grid, dim3(64), 0, stream, q, p.shapes + sphere_table(p.S), table);
+  }
   return hipGetLastError();
 }
 
@@ -2905,10 +3039,17 @@ static_assert(ao_select(64, 20, 8, 200, 2, 2, false, false, false) == AoChoice{0
 static_assert(ao_select(16, 20, 8, 64, 0, 0, false, false, true) == ao_select(16, 20, 8, 64, 0, false, false, true), "no rectangle");
 static_assert(ao_select(16, 20, 9, 65, 1, 0, false, false, false) == ao_select(16, 20, 9, 65, 1, false, false, false), "planes only");
 
+bool ao_takes_pool_list(const FrameParams& p) {
+  return p.mf_n == 0 && (long long)p.trace_rows * p.W < (1ll << 31) &&
+         ao_sorts_by_frame(ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.nrects, p.counters || p.row_counters, false, true).flags);
+}
+
 // Launch ao_batch_kernel<C> over `pools` pools: the LDS rows after the layout hold the sphere
-// table (C::PTW: one 64-sphere word of pre-test rows)
+// table (C::PTW: one 64-sphere word of pre-test rows).  A pool-list launch (q.cull_frames == 2):
+// over the list's blocks.
 template <class C>
 inline void launch_ao(long long pools, hipStream_t stream, const FrameParams& q) {
+  if (q.cull_frames == 2) pools = ao_pool_list_blocks(q.pool_rot, pools - q.pool_rot);
   const dim3 g((unsigned)pools, C::MF ? (unsigned)q.mf_n : 1u);
   hipLaunchKernelGGL((ao_batch_kernel<C>), g, dim3(64), (size_t)batch_lds<C>(q.spp, C::PTW ? 64 : q.nobj).total, stream,
                      q, q.sph, q.cull);
@@ -3525,6 +3666,7 @@ inline FrameParams launch_params(const FrameParams& p) {
     const int TP = kPool / p.spp > 0 ? kPool / p.spp : 1;
     const int ppr = p.W / TP;
     q.pool_rot = ppr >= 8 ? ppr : 8;
+    if (p.cull_frames == 2) q.pool_rot = p.pool_rot;  // a pool-list launch: the list's non-sky pools
   }
   {  // post-process XCD runs (xcd_tile): the least R in [4, gx / 16] dividing gx / 8 (a tile row
     // is a whole number of 8-run rounds, at least two per XCD), else 4; narrow frames: none
@@ -3555,6 +3697,9 @@ inline hipError_t launch_production(int program, const FrameParams& p, const Fra
     const long long pools = (npix + TP - 1) / TP;
     const AoChoice c = ao_select(p.spp, p.D, p.ncl, p.nobj, p.nplanes, p.nrects, p.counters || p.row_counters,
                                  p.mf_n > 0, q.cull != nullptr);
+    // a pool list only with a form that reads it, and counts that are a split of the pools
+    if (q.cull_frames == 2 && (!q.cull || !ao_takes_pool_list(p) || q.pool_rot < 0 || q.pool_rot > pools))
+      return hipErrorInvalidValue;
     // (kSortBit: a build with RT_B1_SORT=0 never selects the sort and compiles no SORT instantiation)
     const bool launched = (c.flags & AO_SORT) ? launch_ao_choice<kSortBit>(c, pools, stream, q, log)
                                               : launch_ao_choice<0>(c, pools, stream, q, log);

@@ -969,6 +969,46 @@ int rt_debug_cull_cache_cap(rt_ctx* c, size_t bytes) {
 
 size_t rt_cull_cache_frame_bytes(rt_ctx* c) { return c ? c->cull.frame_bytes : 0; }
 
+int rt_set_pool_list(rt_ctx* c, int on) {
+  if (!c) return RT_E_INVAL;
+  if (c->cull.list_on == (on != 0)) return RT_OK;
+  RT_HIP(c, hipSetDevice(c->device));
+  c->cull.list_on = on != 0;
+  c->cull.have_key = false;  // the next fill writes the list (or none): the key has to hold anew
+  return c->cull.invalidate(c->last_hip);
+}
+
+int rt_pool_list_stats(rt_ctx* c, long long* builds, long long* list_launches, int* n_nonsky, int* n_sky, size_t* bytes) {
+  if (!c) return RT_E_INVAL;
+  const rt::CullCache& k = c->cull;
+  if (builds) *builds = k.list_builds;
+  if (list_launches) *list_launches = k.list_launches;
+  if (n_nonsky) *n_nonsky = k.list_ready ? k.h_counts[0] : -1;
+  if (n_sky) *n_sky = k.list_ready ? k.h_counts[1] : -1;
+  if (bytes) *bytes = k.list_bytes;
+  return RT_OK;
+}
+
+long long rt_debug_pool_list_read(rt_ctx* c, int what, void* buf, size_t cap) {
+  if (!c || what < 0 || what > 2 || (!buf && cap)) return RT_E_INVAL;
+  const rt::CullCache& k = c->cull;
+  if (!k.valid || (what != 2 && (k.list_bytes == 0 || !(k.list_pending || k.list_ready)))) return RT_E_STATE;
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, hipDeviceSynchronize());  // the fill and the list's build have run
+  const char* const list = (const char*)k.d_alloc;
+  const size_t rows_cap = (size_t)k.list_pools * 16;  // the sky list ends where the rows' bytes end
+  const char* src = (const char*)k.d_table;
+  size_t need = k.bytes;
+  if (what != 2) {
+    int counts[4];
+    RT_HIP(c, hipMemcpy(counts, (const char*)k.d_table - k.frame_bytes - 16, sizeof counts, hipMemcpyDeviceToHost));
+    need = what == 0 ? (size_t)counts[0] * 16 : (size_t)counts[1] * 4;
+    src = what == 0 ? list : list + rows_cap - need;
+  }
+  if (need <= cap && need) RT_HIP(c, hipMemcpy(buf, src, need, hipMemcpyDeviceToHost));
+  return (long long)need;
+}
+
 int rt_debug_launch_log(rt_ctx* c, int on) {
   if (!c) return RT_E_INVAL;
   c->log = on ? &c->launch_log : nullptr;

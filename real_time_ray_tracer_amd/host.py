@@ -373,6 +373,36 @@ class Renderer:
         """Test hook (rt_debug_cull_cache_cap): this context's cap on the cull cache, before its first fill."""
         self._c(self._lib.rt_debug_cull_cache_cap(self.ctx, int(nbytes)), "rt_debug_cull_cache_cap")
 
+    def set_pool_list(self, on: bool):
+        """The cull cache's pool list (rt_set_pool_list; on by default): cached AO launches run one workgroup
+        per non-sky pool and one per 64 sky pools.  Off: one per pool; results are bit-identical."""
+        self._c(self._lib.rt_set_pool_list(self.ctx, int(bool(on))), "rt_set_pool_list")
+
+    def pool_list_stats(self) -> dict:
+        """{"builds", "list_launches", "n_nonsky", "n_sky", "bytes"} (rt_pool_list_stats); the counts are -1
+        while no list's counts have landed."""
+        b, n, ns, sk, by = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_int(), C.c_size_t()
+        self._c(self._lib.rt_pool_list_stats(self.ctx, C.byref(b), C.byref(n), C.byref(ns), C.byref(sk), C.byref(by)),
+                "rt_pool_list_stats")
+        return {"builds": b.value, "list_launches": n.value, "n_nonsky": ns.value, "n_sky": sk.value, "bytes": by.value}
+
+    def debug_pool_list(self) -> dict:
+        """Test hook (rt_debug_pool_list_read), after waiting for the device: {"rows": int32 [n_nonsky][4] of
+        (pb, xf, yf, np), "sky": uint32 [n_sky] in list order, "masks": uint64 [pools][words]} of the current key."""
+        out = {}
+        for what, name, dt in ((0, "rows", np.int32), (1, "sky", np.uint32), (2, "masks", np.uint64)):
+            need = int(self._lib.rt_debug_pool_list_read(self.ctx, what, None, 0))
+            if need < 0:
+                self._c(need, "rt_debug_pool_list_read")
+            a = np.zeros(need // np.dtype(dt).itemsize, dt)
+            if need:
+                self._c(min(0, int(self._lib.rt_debug_pool_list_read(self.ctx, what, a.ctypes.data_as(C.c_void_p), need))),
+                        "rt_debug_pool_list_read")
+            out[name] = a
+        out["rows"] = out["rows"].reshape(-1, 4)
+        out["sky"] = out["sky"][::-1].copy()  # stored downwards from the rows' end
+        return out
+
     def set_launch_log(self, on: bool):
         """Test hook (rt_debug_launch_log): record the form of every kernel this context launches; off empties the log."""
         self._c(self._lib.rt_debug_launch_log(self.ctx, int(bool(on))), "rt_debug_launch_log")
@@ -702,6 +732,10 @@ class StripGroup:
         """Renderer.set_query_tree on every strip (rt_group_set_query_tree); kept when the strips are
         re-created."""
         self._c(self._lib.rt_group_set_query_tree(self.g, int(bool(on))), "rt_group_set_query_tree")
+
+    def set_pool_list(self, on: bool):
+        """Renderer.set_pool_list on every strip (rt_group_set_pool_list); kept when the strips are re-created."""
+        self._c(self._lib.rt_group_set_pool_list(self.g, int(bool(on))), "rt_group_set_pool_list")
 
     def bind_frame(self, device_ptr: int | None):
         self._c(self._lib.rt_group_bind_frame(self.g, C.c_void_p(device_ptr) if device_ptr else None),
